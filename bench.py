@@ -7,14 +7,20 @@ TRPO update (pg, 10-iteration CG on the Fisher product, step scaling, line searc
 Inputs are synthetic (random-init nets, simulator-generated data); all device work
 starts from state already resident in HBM.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...      (one rank per GPU, RCCL)
 
 Rank 0 prints ONE JSON line.  value = env-steps/s summed over ranks (weak scaling:
 E x T envs-steps per GPU per iteration).  Also reported: TRPO-iters/s, per-phase
-times, the live HIP-event roofline of the dominant kernel (by device time per iteration:
-the persistent rollout on C3) and of the GAE scan, and the CPU oracle timed on a bounded
-sample of the workload.  Defaults: N = 1, K = 20, W = 5 (well under a minute of GPU time).
+times and the live HIP-event roofline of the dominant kernel (by device time per iteration:
+the persistent rollout on C3), all from events recorded inside the timed region.
+Defaults: N = 1, K = 20, W = 5 (well under a minute of GPU time).
+
+A plain run sets up, warms up, times the K iterations and prints the line.  ``--full``
+adds what takes runs of its own after the timed region: the GAE scan's back-to-back
+roofline (``roofline_gae``) and the CPU oracle timed on a bounded sample of the workload
+(``cpu_baseline``; ``--no-cpu-baseline`` leaves that one out).  ``--dump-outputs DIR``
+writes what the last timed iteration computed as DIR/<name>.npy (``dump_outputs``).
 """
 import argparse
 import gc
@@ -349,6 +355,37 @@ def policy_gemm_roofline(kern, kinfo, net, dtype, n_rows, K, pmc, gemm_pmc):
                        "MFMA) against the bf16 peak" if split else "")}
 
 
+DUMP_ROWS = 65536            # batch rows written by --dump-outputs (a seeded sample of the E x T rows)
+DUMP_ROW_BYTES = 32 << 20    # ... fewer when the rows are wide: at most this many bytes of rows in all
+
+
+def dump_outputs(out_dir, agent, batch, stats):
+    """What the last timed iteration computed, as ``out_dir/<name>.npy`` in float32 (stats:
+    float64): the policy's and the VF's flat parameters after their last update / fit, the
+    iteration's scalar stats (names in stats_names.json), and a fixed sample (seeded, the
+    same rows every run) of the last batch's time-major rows -- observations, actions,
+    action-distribution parameters, rewards, episode flags, V predictions, GAE advantages
+    (standardised) and returns.  Well under 64 MB in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    cols = {k: getattr(batch, k) for k in ("obs", "act", "prob", "rew", "flags", "vpred", "adv", "ret")}
+    width = sum(v.reshape(batch.n, -1).shape[1] for v in cols.values())
+    rows = min(batch.n, DUMP_ROWS, DUMP_ROW_BYTES // (4 * width))
+    idx = np.sort(np.random.default_rng(0).choice(batch.n, size=rows, replace=False))
+    out = {"policy_theta": agent.policy.net.get_flat().astype(np.float32),
+           "vf_theta": agent.baseline.net.get_flat().astype(np.float32),
+           "batch_rows": idx.astype(np.float64)}
+    sel = torch.as_tensor(idx, device=batch.obs.device)
+    for k, v in cols.items():
+        out["batch_" + k] = v.reshape(batch.n, -1)[sel].float().cpu().numpy()
+    names = [k for k, v in (stats or {}).items() if isinstance(v, (int, float, np.integer, np.floating))]
+    out["stats"] = np.array([float(stats[k]) for k in names], dtype=np.float64)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    with open(os.path.join(out_dir, "stats_names.json"), "w") as f:
+        json.dump(names, f)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -362,7 +399,12 @@ def main():
     ap.add_argument("--hid", default=None, help="hidden sizes, e.g. 512,512,512 (default 64,64; Humanoid 512x3)")
     ap.add_argument("--cpu-envs", type=int, default=None)
     ap.add_argument("--cpu-horizon", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU oracle's timing out")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed iterations also time the GAE scan back to back (roofline_gae) and the "
+                         "CPU oracle on a bounded sample of the workload (cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed iteration computed as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"],
                     help="MFMA operand precision of every MLP pass (fp32: the parity dtype; bf16: throughput mode)")
     ap.add_argument("--no-pipeline", action="store_true",
@@ -403,6 +445,7 @@ def main():
     spans = {"rollout": ("rollout0", "rollout1"), "advantage": ("adv0", "adv1"), "vf_fit": ("vf0", "vf1"),
              "trpo_update": ("upd0", "upd1")}
     recs = []
+    last_stats = None
 
     with runner.loop_stream():  # no legacy-stream operations between the steps (IterationRunner.loop_stream)
         for i in range(args.warmup):
@@ -422,13 +465,16 @@ def main():
     with runner.loop_stream():
         for i in range(args.steps):
             timing.tick()
-            runner.step(prelaunch_next=i + 1 < args.steps)  # the next rollout issued as theta is final
+            last_stats = runner.step(prelaunch_next=i + 1 < args.steps)  # the next rollout issued as theta is final
             recs.append(runner.last_phase_events)
-        runner.drain()
+        last_stats = runner.drain() or last_stats  # pipelined: the last iteration's stats come with its VF fit
     recs.append(runner.last_drain_events if runner.pipeline else {})
     torch.cuda.synchronize()
     comm.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        # before anything below reruns a kernel on the last batch (--full: the GAE scan)
+        dump_outputs(args.dump_outputs, agent, runner.last_batch, last_stats)
     if comm.enabled:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -522,7 +568,7 @@ def main():
             gemm_pmc = json.load(f).get(f"{args.env}/{args.dtype}/{E}", {})
     pg_roof = policy_gemm_roofline(kern, kinfo, net, args.dtype, n_local, K, pmc, gemm_pmc)
     gae = None
-    if "gae_scan" in kern:
+    if args.full and "gae_scan" in kern:
         cnt, mean_ms, _ = kern["gae_scan"]
         # the scan launched back to back on the last iteration's batch, one HIP event pair
         # around 20 launches on its stream: the kernel's own duration (the in-loop region
@@ -558,7 +604,7 @@ def main():
         "roofline_gae": gae,
         "roofline_policy_gemm": pg_roof,
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(cpu_E, cpu_T, args.env, hid)
         line["cpu_baseline"]["serial_c1"] = cpu_serial_c1()
     json_out.write(json.dumps(line) + "\n")

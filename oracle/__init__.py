@@ -7,7 +7,7 @@ this repository.  Every function cites the reference file:line it restates.
 Who may import it (and nobody else):
   * ``tests/``                       -- as the parity checker,
   * ``__graft_entry__.smoke()``       -- as the checker of one small invocation,
-  * ``bench.py`` ``cpu_baseline`` leg -- timed as the reported CPU baseline.
+  * ``bench.py --full`` ``cpu_baseline`` leg -- timed as the reported CPU baseline.
 
 The product package ``modular_rl_amd`` never imports this; its compute path is
 the HIP library ``libmrl_hip.so`` and fails loudly when that is missing.

@@ -35,7 +35,7 @@ for step in "$@"; do
       timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread \
         > gpurun_out/${tag}_tests.log 2>&1 || { echo TESTS_FAILED; tail -40 gpurun_out/${tag}_tests.log; exit 1; }
       tail -1 gpurun_out/${tag}_tests.log ;;
-    hopper) bench hopper 400 ;;
+    hopper) bench hopper 400 --full ;;
     prof)
       timeout -k 10 400 rocprofv3 --kernel-trace --stats -d gpurun_out/${tag}_prof -o run --output-format csv \
         -- python3 bench.py --steps 10 --warmup 1 --no-cpu-baseline > gpurun_out/${tag}_prof.log 2>&1 ||
@@ -54,11 +54,11 @@ for step in "$@"; do
         --out gpurun_out/${tag}_pmc.json > /dev/null && echo PMC_OK
       unset MRL_XSTREAM_EVENT ;;
     lines)
-      bench hopper_bf16 400 --dtype bf16 --no-cpu-baseline
-      bench cartpole_bf16 400 --env CartPole-v0 --dtype bf16 --no-cpu-baseline
-      bench cartpole 400 --env CartPole-v0 --no-cpu-baseline
-      bench humanoid_bf16 500 --env Humanoid-v2 --envs 1024 --hid 512,512,512 --steps 10 --warmup 1 --dtype bf16 --no-cpu-baseline
-      bench humanoid 600 --env Humanoid-v2 --envs 1024 --hid 512,512,512 --steps 5 --warmup 1 --no-cpu-baseline ;;
+      bench hopper_bf16 400 --full --dtype bf16 --no-cpu-baseline
+      bench cartpole_bf16 400 --full --env CartPole-v0 --dtype bf16 --no-cpu-baseline
+      bench cartpole 400 --full --env CartPole-v0 --no-cpu-baseline
+      bench humanoid_bf16 500 --full --env Humanoid-v2 --envs 1024 --hid 512,512,512 --steps 10 --warmup 1 --dtype bf16 --no-cpu-baseline
+      bench humanoid 600 --full --env Humanoid-v2 --envs 1024 --hid 512,512,512 --steps 5 --warmup 1 --no-cpu-baseline ;;
     sq)  # SQ wave-time split of the Fisher-product kernels (one 8-counter pass of the probe)
       timeout -s KILL 200 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY \
         SQ_WAIT_INST_LDS SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_BUSY_CYCLES --output-format csv \
@@ -97,7 +97,7 @@ for step in "$@"; do
           -- python3 tools/gae_probe.py >> gpurun_out/${tag}_gae.log 2>&1 || { tail -5 gpurun_out/${tag}_gae.log; exit 1; }
       grep -v amdgpu.ids gpurun_out/${tag}_gae.log | grep gae
       grep -h gae gpurun_out/${tag}_gae_prof/run_kernel_stats.csv ;;
-    pair) MRL_FISHER_ONEPASS=0 bench pair 400 --no-cpu-baseline ;;
+    pair) MRL_FISHER_ONEPASS=0 bench pair 400 --full --no-cpu-baseline ;;
     layered_tests)
       timeout -k 10 900 python -u -m pytest tests/test_gpu_layered.py tests/test_gpu_humanoid.py -m gpu -x -q \
         --timeout 300 --timeout-method thread > gpurun_out/${tag}_layered_tests.log 2>&1 ||
@@ -109,8 +109,8 @@ for step in "$@"; do
         --no-cpu-baseline > gpurun_out/${tag}_c5prof.log 2>&1 || { echo C5PROF_FAILED; tail -5 gpurun_out/${tag}_c5prof.log; exit 1; }
       python tools/step_timeline.py gpurun_out/${tag}_c5prof/run_kernel_trace.csv > gpurun_out/${tag}_c5_timeline.txt &&
         cat gpurun_out/${tag}_c5_timeline.txt ;;
-    c5) bench humanoid 600 --env Humanoid-v2 --envs 1024 --hid 512,512,512 --steps 5 --warmup 1 --no-cpu-baseline ;;
-    c5_f32) MRL_GEMM_SPLIT=0 bench humanoid_f32gemm 600 --env Humanoid-v2 --envs 1024 --hid 512,512,512 --steps 5 \
+    c5) bench humanoid 600 --full --env Humanoid-v2 --envs 1024 --hid 512,512,512 --steps 5 --warmup 1 --no-cpu-baseline ;;
+    c5_f32) MRL_GEMM_SPLIT=0 bench humanoid_f32gemm 600 --full --env Humanoid-v2 --envs 1024 --hid 512,512,512 --steps 5 \
       --warmup 1 --no-cpu-baseline ;;
     det)
       REPS=8 timeout -k 10 200 python -u tools/det_locate.py > gpurun_out/${tag}_det.log 2>&1 ||
