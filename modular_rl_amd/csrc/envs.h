@@ -80,38 +80,17 @@ constexpr double HP_MB[4] = {HP_MB0, HP_MB1, HP_MB2, HP_MB3};
 constexpr double HP_IMT = 1.0 / HP_MB0;
 
 // a0..a3 by k.  With k a run-time lane value (HopperQuad: the lane's row) the select
-// tree is formed from bit masks the optimiser cannot see through: a plain ternary chain
-// on doubles was compiled into a switch on k -- exec-masked branches around every
-// selection, all four arms issued by the divergent rows, about a dozen times per
-// substep.  Exact either way (a selection).
-__device__ inline double pick_bits(uint32_t m, double x, double y) {  // m ? y : x, m all ones or zero
-  const uint64_t xb = (uint64_t)__double_as_longlong(x), yb = (uint64_t)__double_as_longlong(y);
-  const uint32_t lo = ((uint32_t)yb & m) | ((uint32_t)xb & ~m);
-  const uint32_t hi = ((uint32_t)(yb >> 32) & m) | ((uint32_t)(xb >> 32) & ~m);
-  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-#ifndef MRL_HP_SEL_BITS  // 0: the plain ternary chain (A/B: r04x rollout 13.87 ms with, 14.05 without);
-#define MRL_HP_SEL_BITS 2  // 1: bit masks made opaque per call; 2: selects on k's bits
-#endif
-#ifndef MRL_HP_LIM_BITS  // 1: joint limits and the health test without branches as well (measured
-#define MRL_HP_LIM_BITS 0  // slower: 14.56 ms, the extra live values spill)
-#endif
-#ifndef MRL_HP_LIM_SEL  // 1: joint limits as selects over both evaluated forms (0: the ternary)
-#define MRL_HP_LIM_SEL 1
-#endif
-#ifndef MRL_HP_HEALTH_BITS  // 1: the health test's comparisons combined with & (no branches)
-#define MRL_HP_HEALTH_BITS 1
-#endif
+// tree is formed on k's two bits: a plain ternary chain on doubles was compiled into a
+// switch on k -- exec-masked branches around every selection, all four arms issued by
+// the divergent rows, about a dozen times per substep.  Exact either way (a selection).
+// Measured and rejected: the ternary chain, and opaque bit-mask selects for
+// sel4, the joint limits and the health test.
 __device__ inline double sel4(int k, double a0, double a1, double a2, double a3) {
-  if (!MRL_HP_SEL_BITS || __builtin_constant_p(k)) return k == 0 ? a0 : (k == 1 ? a1 : (k == 2 ? a2 : a3));
-  if (MRL_HP_SEL_BITS == 2) {  // selects on k's two bits (v_cndmask on loop-invariant lane masks)
-    const bool b0 = (k & 1) != 0, b1 = (k & 2) != 0;
-    const double lo = b0 ? a1 : a0, hi = b0 ? a3 : a2;
-    return b1 ? hi : lo;
-  }
-  uint32_t m0 = 0u - (uint32_t)(k & 1), m1 = 0u - (uint32_t)((k >> 1) & 1);
-  asm volatile("" : "+v"(m0), "+v"(m1));
-  return pick_bits(m1, pick_bits(m0, a0, a1), pick_bits(m0, a2, a3));
+  if (__builtin_constant_p(k)) return k == 0 ? a0 : (k == 1 ? a1 : (k == 2 ? a2 : a3));
+  // selects on k's two bits (v_cndmask on loop-invariant lane masks)
+  const bool b0 = (k & 1) != 0, b1 = (k & 2) != 0;
+  const double lo = b0 ? a1 : a0, hi = b0 ? a3 : a2;
+  return b1 ? hi : lo;
 }
 
 __device__ inline void hopper_reset(const double* u, double* s) {
@@ -232,16 +211,8 @@ __device__ inline void hopper_substep(double* q, double* v, const double* tau, c
   phi[0] = q[2];
 #pragma unroll
   for (int j = 1; j < 4; ++j) phi[j] = phi[j - 1] - q[2 + j];
-#ifdef MRL_HP_ABL_NOSINCOS  // diagnostic timing build only (results are wrong)
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    sg[k] = phi[k] - phi[k] * phi[k] * phi[k] * (1.0 / 6.0);
-    cg[k] = 1.0 - phi[k] * phi[k] * 0.5;
-  }
-#else
   double s_own = 0.0, c_own = 0.0;  // HopperQuad: the row's own segment's sin / cos
   par.sincos4(phi, sg, cg, s_own, c_own);
-#endif
   om[0] = v[2];
 #pragma unroll
   for (int j = 1; j < 4; ++j) om[j] = om[j - 1] - v[2 + j];
@@ -276,11 +247,6 @@ __device__ inline void hopper_substep(double* q, double* v, const double* tau, c
     paz[j + 1] = fmad(-w2, gz[j], paz[j]);
   }
   double ct[4][3];
-#ifdef MRL_HP_ABL_NOCONTACT  // diagnostic timing build only (results are wrong)
-#pragma unroll
-  for (int k = 0; k < 4; ++k) ct[k][0] = ct[k][1] = ct[k][2] = pz[k] * 1e-3;
-  if (false)
-#endif
   par.contacts(
       [&](int k, double* out) {
         hopper_contacts(par.capsule(k), sel4(k, pz[0], pz[1], pz[2], pz[3]), sel4(k, pvx[0], pvx[1], pvx[2], pvx[3]),
@@ -348,25 +314,12 @@ __device__ inline void hopper_substep(double* q, double* v, const double* tau, c
   for (int i = 1; i < 4; ++i) {
     const int jj = i - 1, j = 2 + i;
     C[i][i] = C[i][i] + HP_ARM;
-#if MRL_HP_LIM_SEL
     // joint-limit force: both one-sided forms evaluated, the active one picked by a plain
     // select (v_cndmask) -- the ternary over the fmas was an exec-masked branch pair per
     // joint, both arms issued by divergent rows
     const double cv = -(HP_CL * v[j]);
     const double flo = fmad(HP_KL, HP_LO[jj] - q[j], cv), fhi = fmad(HP_KL, HP_HI[jj] - q[j], cv);
     const double lim = q[j] < HP_LO[jj] ? flo : (q[j] > HP_HI[jj] ? fhi : 0.0);
-#elif MRL_HP_LIM_BITS
-    // joint-limit force: both one-sided forms evaluated, the active one selected by bit
-    // masks (divergent rows make the ternary an exec-masked branch pair per joint)
-    const double cv = -(HP_CL * v[j]);
-    const double flo = fmad(HP_KL, HP_LO[jj] - q[j], cv), fhi = fmad(HP_KL, HP_HI[jj] - q[j], cv);
-    uint32_t mlo = q[j] < HP_LO[jj] ? ~0u : 0u, mhi = q[j] > HP_HI[jj] ? ~0u : 0u;
-    asm volatile("" : "+v"(mlo), "+v"(mhi));
-    const double lim = pick_bits(mlo, pick_bits(mhi, 0.0, fhi), flo);
-#else
-    const double lim = q[j] < HP_LO[jj] ? fmad(HP_KL, HP_LO[jj] - q[j], -(HP_CL * v[j]))
-                                        : (q[j] > HP_HI[jj] ? fmad(HP_KL, HP_HI[jj] - q[j], -(HP_CL * v[j])) : 0.0);
-#endif
     rhs[j] = fmad(-HP_DAMP, v[j], rhs[j] + tau[jj]) + lim;
   }
   // Schur complement of the translational block, 4x4 LDL^T (oracle hopper_solve)
@@ -380,12 +333,7 @@ __device__ inline void hopper_substep(double* q, double* v, const double* tau, c
     }
 #pragma unroll
   for (int a = 0; a < 4; ++a) rr[a] = fmad(-fmad(B0[a], rhs[0], B1[a] * rhs[1]), HP_IMT, rhs[2 + a]);
-#ifdef MRL_HP_ABL_NOLDL  // diagnostic timing build only (results are wrong)
-#pragma unroll
-  for (int a = 0; a < 4; ++a) x[a] = rr[a] * K[a][a];
-#else
   ldl_solve4(K, rr, x);
-#endif
   const double t0 = rhs[0] - fmad(B0[3], x[3], fmad(B0[2], x[2], fmad(B0[1], x[1], B0[0] * x[0])));
   const double t1 = rhs[1] - fmad(B1[3], x[3], fmad(B1[2], x[2], fmad(B1[1], x[1], B1[0] * x[0])));
   const double qdd[6] = {t0 * HP_IMT, t1 * HP_IMT, x[0], x[1], x[2], x[3]};
@@ -407,7 +355,7 @@ __device__ inline void hopper_step(double* s, const float* a, double& rew, bool&
   for (int k = 0; k < HP_FRAME_SKIP; ++k) hopper_substep(q, v, tau, par);
   rew = (q[0] - x_before) / (HP_DT * HP_FRAME_SKIP) + 1.0 - 1e-3 * asq;
   bool healthy = true;
-#if MRL_HP_LIM_BITS || MRL_HP_HEALTH_BITS  // every test evaluated and combined with & (the && chain: nested branches)
+  // every test evaluated and combined with & (an && chain compiles to nested branches)
   // |s_i| < 100 is false for a NaN or an infinity, so isfinite(s_i) adds nothing for
   // i >= 2: the same truth value from 14 comparisons instead of 24, combined as a
   // balanced tree (depth 4) instead of a chain
@@ -423,11 +371,6 @@ __device__ inline void hopper_step(double* s, const float* a, double& rew, bool&
 #pragma unroll
     for (int i = 0; i + w < 14; i += 2 * w) t[i] = t[i] & t[i + w];
   healthy = t[0];
-#else
-  for (int i = 0; i < 12; ++i) healthy = healthy && isfinite(s[i]);
-  for (int i = 2; i < 12; ++i) healthy = healthy && (fabs(s[i]) < 100.0);
-  healthy = healthy && (q[1] > 0.7) && (fabs(q[2]) < 0.2);
-#endif
   done = !healthy;
 }
 

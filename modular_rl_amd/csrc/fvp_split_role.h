@@ -1,6 +1,6 @@
 // The Fisher product's JVP half on split bf16 operands, as a per-tile role shared by the
 // standalone JVP rows kernel (mlp_split.hip: mlp_fvp_split_kernel) and the one-pass
-// Fisher product (mlp_kernels.hip: mlp_fisher_hyb_kernel).  Exact three-way bf16 splits
+// Fisher product (mlp_fisher.hip: mlp_fisher_hyb_kernel).  Exact three-way bf16 splits
 // of every f32 MFMA operand, six part products on bf16 MFMA (mlp_split.hip header).
 #pragma once
 #include "../../include/mrl_hip.h"
@@ -161,7 +161,7 @@ struct JvpSplitRole {
   // tile `tile` (its x / h1 already loaded), prefetching tile tn's (tn == tile: re-read);
   // PF = false: no prefetch -- the tile's own x / h1 are loaded here, after its h2 (and no
   // prologue), so the tile's bytes all enter L2 within one round (the one-pass product's
-  // VJP role re-reads them a round later: MRL_FISHER_JVP_PF)
+  // VJP role re-reads them a round later: mlp_fisher.hip)
   template <bool PF = true, class Sink>
   __device__ __forceinline__ void tile(int64_t tile, int64_t tn, Sink&& sink) {
     const int64_t row = tile * 32 + (lane & 31);
@@ -302,9 +302,5 @@ __device__ __forceinline__ void split_rows_tile(const RowsArgs& a, const BDims& 
     if (a.feat != nullptr && valid) write_feature_row(a, row, h, xl);
   if (valid && h == 0) row_epilogue<EPI, MAX_OUT, LDSHEAD>(ae, erow, z, dz, ls, sd, dls, acc0, acc1, acc2);
 }
-
-// launch mlp_rows_split_kernel<epi, sh> (mlp_split.hip) for mrl_mlp_rows_split
-int launch_rows_split(int epi, int sh, const RowsArgs& a, const BDims& b, const float* image_s, int64_t blocks,
-                      const int32_t* skip, void* stream);
 
 }  // namespace mrl

@@ -557,19 +557,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_big_kernel(GemmB16Args g, Bi
     // 16p + 8h .. + 7: half the store instructions, 16-B bf16 stores (the epilogue is
     // store-issue-bound: 8-B stores ran 1.1-1.2 x slower).  The next tile's first stages
     // are already in flight.
-#ifdef MRL_BIG_ABL_NOEPI  // diagnostic timing build only (tools/build_ablate.sh): no epilogue
-    {
-      float sacc = 0.f;
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) sacc += acc[mi][ni][r];
-      if (sacc == 1234.5f) reinterpret_cast<float*>(g.C)[tm] = sacc;
-      continue;
-    }
-#endif
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi) {
       const int64_t row = tm * BBM + 64 * wm + 32 * mi + j;

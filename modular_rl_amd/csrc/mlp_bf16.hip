@@ -1,11 +1,11 @@
 // bf16 throughput mode of the fused 64-wide MLP kernels (MRL_COMPUTE_BF16): the same
-// passes as mlp_kernels.hip (forward + row epilogues, Fisher-product JVP, VJP) on
-// v_mfma_f32_32x32x16_bf16 -- 16x the f32 MFMA rate -- with f32 accumulation.
+// passes as the f32 kernels of mlp_rows_vjp.hip (forward + row epilogues, Fisher-product
+// JVP, VJP) on v_mfma_f32_32x32x16_bf16 -- 16x the f32 MFMA rate -- with f32 accumulation.
 //
 // Rounding points (bf16 RNE): the weights W0, W1 (and the tangent's dW0, dW1), the
 // layer inputs x, h1, h2 and the backpropagated head rows / layer-2 gradients that
 // enter an MFMA.  Biases, tanh, tanh', the head layer (n_out <= 8, f32 VALU on the
-// bf16-rounded h2) and every row epilogue stay f32.  fp32 (mlp_kernels.hip) is the
+// bf16-rounded h2) and every row epilogue stay f32.  fp32 (mlp_rows_vjp.hip) is the
 // parity dtype; this mode is checked against the fp64 oracle at a bf16 bound
 // (tests/test_gpu_bf16.py).
 //
@@ -29,6 +29,7 @@
 #include "mlp_device.h"
 #include "rows_epilogue.h"
 #include "bf16_frag.h"
+#include "mlp_host.h"
 
 namespace mrl {
 
@@ -179,20 +180,12 @@ __device__ inline void rows_shape_b(RowsArgs& a, BDims& b) {
 // of the static shapes -- it waits on memory for half its wave time and a third wave
 // hides some of it (CartPole 0.313 -> 0.265 ms, Hopper 0.353 -> 0.286 ms at 4.19 M
 // rows; Hopper's spills 16 bytes a lane) -- 2 for the others (the loss / gradient passes
-// measured level or slower at 3; the run-time shape and the uncached FVP pass spill)
-#ifndef MRL_ROWS_B_OCC3
-#define MRL_ROWS_B_OCC3 1
-#endif
-// MRL_ROWS_B_OCC4=1: the PROB / LOSSES / SURRGRAD passes of the static shapes at 4 waves
-// (48-64 bytes a lane spilled).  Measured and not kept (tools/occ4_ab.sh): SURRGRAD
-// 0.47 -> 0.50 ms (CartPole), 0.52 -> 0.58 ms (Hopper); PROB level
-#ifndef MRL_ROWS_B_OCC4
-#define MRL_ROWS_B_OCC4 0
-#endif
+// measured level or slower at 3; the run-time shape and the uncached FVP pass spill).
+// Measured and not kept: the PROB / LOSSES / SURRGRAD passes of the static
+// shapes at 4 waves.
 template <int EPI_K, int SH>
 constexpr int rows_b_occ() {
-  if (MRL_ROWS_B_OCC4 && (SH & ~SH_TIME) != 0 && EPI_K <= MRL_EPI_SURRGRAD) return 4;
-  return (MRL_ROWS_B_OCC3 && (SH & ~SH_TIME) != 0 && EPI_K == EPI_FVP_CACHED_B) ? 3 : 2;
+  return ((SH & ~SH_TIME) != 0 && EPI_K == EPI_FVP_CACHED_B) ? 3 : 2;
 }
 
 template <int EPI_K, int SH>
@@ -637,67 +630,43 @@ __global__ __launch_bounds__(256, 1) void mlp_vjp_bf16_kernel(VjpArgsB a_in, con
 
 using namespace mrl;
 
-static int check_desc_b(const mrl_mlp_desc* d) {
-  if (d == nullptr) return fail(E_ARG, "null mlp desc");
-  if (d->n_hidden != HID || d->n_layers != 2)
-    return fail(E_UNSUPPORTED, "only hid_sizes=[64,64] is implemented on the fused HIP path");
-  if (d->n_in < 1 || d->n_in > MAX_IN) return fail(E_UNSUPPORTED, "n_in must be in [1, 32]");
-  if (d->n_out < 1 || d->n_out > MAX_OUT) return fail(E_UNSUPPORTED, "n_out must be in [1, 8]");
-  if (d->head < 0 || d->head > 2) return fail(E_ARG, "bad head kind");
-  if (d->head == MRL_HEAD_LINEAR && d->n_out != 1) return fail(E_ARG, "linear head needs n_out=1");
-  if (d->cus < 0 || d->cus > 1024) return fail(E_ARG, "cus must be in [0, 1024]");
-  return OK;
-}
-
-static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 // Grid caps, swept with tools/fvp_probe.py at 4.19 M rows (MRL_ROWS_BF16_BLOCKS
 // overrides both): the Fisher-product JVP (154 VGPRs: 3 blocks per CU) is fastest at
 // exactly one resident round (768: 0.347 ms; 1024: 0.47, 1536: 0.356, 2048: 0.395);
 // the forward passes (≤ 128 VGPRs) at three rounds and more (3072: surrgrad 0.526,
 // prob 0.299 ms; 2048: 0.538 / 0.303).
 constexpr int ROWS_FVP_BLOCKS_B = 768;
-// caps per 256 CUs, scaled by the desc's `cus` (mlp_kernels.hip desc_cus)
-static int64_t desc_cus_b(const mrl_mlp_desc* d) { return d != nullptr && d->cus > 0 ? d->cus : 256; }
-static int64_t scaled_cap(int64_t cap, int64_t cus) { return cap * cus / 256 > 0 ? cap * cus / 256 : 1; }
+// caps per 256 CUs, scaled by the desc's `cus` (mlp_host.h)
 static int64_t rows_blocks_b(int64_t n, bool fvp = false, int64_t cus = 256) {
   static const int64_t env_cap = [] {
     const char* e = getenv("MRL_ROWS_BF16_BLOCKS");
     return (int64_t)(e ? atoi(e) : 0);
   }();
-  const int64_t cap = env_cap > 0 ? env_cap : scaled_cap(fvp ? ROWS_FVP_BLOCKS_B : ROWS_MAX_BLOCKS_B, cus);
-  int64_t g = cdiv(cdiv(n, 32), 4);
-  if (g < 1) g = 1;
-  return g > cap ? cap : g;
+  return grid_blocks(n, env_cap > 0 ? env_cap : scaled_cap(fvp ? ROWS_FVP_BLOCKS_B : ROWS_MAX_BLOCKS_B, cus));
 }
-static int64_t vjp_blocks_b(int64_t n, int64_t cus = 256) {
-  int64_t g = cdiv(cdiv(n, 32), 4);
-  if (g < 1) g = 1;
-  const int64_t cap = scaled_cap(VJP_MAX_BLOCKS_B, cus);
-  return g > cap ? cap : g;
-}
+static int64_t vjp_blocks_b(int64_t n, int64_t cus = 256) { return grid_blocks(n, scaled_cap(VJP_MAX_BLOCKS_B, cus)); }
 
 extern "C" {
 
 int64_t mrl_mlp_image_words_bf16(const mrl_mlp_desc* d) {
-  if (check_desc_b(d) != OK) return -1;
+  if (check_desc(d) != OK) return -1;
   return bf16_dims(d->n_in, d->n_out).total_words;
 }
-int64_t mrl_act_cache_words_bf16(int64_t n) { return cdiv(n, 32) * BCACHE_TILE_WORDS; }
+int64_t mrl_act_cache_words_bf16(int64_t n) { return ceil_div(n, 32) * BCACHE_TILE_WORDS; }
 int64_t mrl_partial_rows_bf16(int64_t n) { return rows_blocks_b(n) * 4; }
 int64_t mrl_slab_rows_bf16(int64_t n) { return vjp_blocks_b(n) * 4; }
 int64_t mrl_mlp_partial_rows_bf16(const mrl_mlp_desc* d, int64_t n) {
-  if (check_desc_b(d) != OK) return -1;
-  return rows_blocks_b(n, false, desc_cus_b(d)) * 4;
+  if (check_desc(d) != OK) return -1;
+  return rows_blocks_b(n, false, desc_cus(d)) * 4;
 }
 int64_t mrl_mlp_slab_rows_bf16(const mrl_mlp_desc* d, int64_t n) {
-  if (check_desc_b(d) != OK) return -1;
-  return vjp_blocks_b(n, desc_cus_b(d)) * 4;
+  if (check_desc(d) != OK) return -1;
+  return vjp_blocks_b(n, desc_cus(d)) * 4;
 }
 
 int mrl_mlp_pack_bf16(const mrl_mlp_desc* d, const float* theta, float* image, int32_t fwd_only,
                       const int32_t* skip, void* stream) {
-  int rc = check_desc_b(d);
+  int rc = check_desc(d);
   if (rc) return rc;
   if (!theta || !image) return fail(E_ARG, "null pointer");
   const MlpDims m = mlp_dims(d->n_in, d->n_out, d->head == MRL_HEAD_GAUSS);
@@ -711,7 +680,7 @@ int mrl_mlp_pack_bf16(const mrl_mlp_desc* d, const float* theta, float* image, i
 int mrl_mlp_rows_bf16(const mrl_mlp_desc* d, int32_t epi, const float* theta, const float* image,
                       const float* tangent, const float* image_t, const mrl_rows_io* io, const int32_t* skip,
                       void* stream) {
-  int rc = check_desc_b(d);
+  int rc = check_desc(d);
   if (rc) return rc;
   if (!io || !image || !io->x) return fail(E_ARG, "null pointer");
   if (io->n <= 0) return OK;
@@ -776,7 +745,7 @@ int mrl_mlp_rows_bf16(const mrl_mlp_desc* d, int32_t epi, const float* theta, co
   const BDims b = bf16_dims(d->n_in, d->n_out);
   const size_t shm = (size_t)b.fwd_words * 4 * (epi == MRL_EPI_FVP ? 2 : 1);
   hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(epi == MRL_EPI_PPOSGD ? 1 : rows_blocks_b(io->n, epi == MRL_EPI_FVP, io->partial != nullptr ? desc_cus_b(d) : 256)),
+  const dim3 grid(epi == MRL_EPI_PPOSGD ? 1 : rows_blocks_b(io->n, epi == MRL_EPI_FVP, io->partial != nullptr ? desc_cus(d) : 256)),
       blk(ROWS_BLOCK_B);
   // the benchmark nets as static shapes (plain rows; a time-feature column built from
   // ep_t takes the generic kernel); policy epilogues only for the policy shapes
@@ -821,7 +790,7 @@ int mrl_mlp_rows_bf16(const mrl_mlp_desc* d, int32_t epi, const float* theta, co
 int mrl_mlp_vjp_bf16(const mrl_mlp_desc* d, const float* image, const float* x, const int32_t* ep_t, double ts_limit,
                      const float* ghead, int64_t n, float* slab, const float* act_cache, const int32_t* skip,
                      void* stream) {
-  int rc = check_desc_b(d);
+  int rc = check_desc(d);
   if (rc) return rc;
   if (!image || !x || !ghead || !slab) return fail(E_ARG, "null pointer");
   if (n <= 0) return OK;
@@ -839,7 +808,7 @@ int mrl_mlp_vjp_bf16(const mrl_mlp_desc* d, const float* image, const float* x, 
   a.slab = slab;
   a.cache = act_cache;
   const size_t shm = (size_t)a.b.total_words * 4;
-  const dim3 grid(vjp_blocks_b(n, desc_cus_b(d))), blk(256);
+  const dim3 grid(vjp_blocks_b(n, desc_cus(d))), blk(256);
   hipStream_t s = (hipStream_t)stream;
   // the benchmark policies and value nets as static shapes (plain rows only: the VF
   // fit reads its materialised [obs, t / limit] rows; a time feature built from ep_t

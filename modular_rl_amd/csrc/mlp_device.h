@@ -203,13 +203,9 @@ __device__ inline bf16x8 W8(const bf16x16& w) { return __builtin_shufflevector(w
 
 // tanh' from the activation, 1 - h^2, as one explicit fma (see tanh_fast)
 __device__ inline float dtanh(float h) { return fmaf(-h, h, 1.f); }
-#ifndef MRL_PK_DTANH  // 1: tile products with tanh' on packed f32 pairs
-#define MRL_PK_DTANH 1
-#endif
 // t[r] *= 1 - h[r]^2 over a 16-float C tile: v_pk_fma / v_pk_mul on pairs, each
 // element rounded exactly as t[r] * dtanh(h[r])
 __device__ inline void mul_dtanh16(f32x16& t, const f32x16& h) {
-#if MRL_PK_DTANH
 #pragma unroll
   for (int r = 0; r < 16; r += 2) {
     const f32x2 hh = f32x2{h[r], h[r + 1]};
@@ -218,10 +214,6 @@ __device__ inline void mul_dtanh16(f32x16& t, const f32x16& h) {
     t[r] = tt.x;
     t[r + 1] = tt.y;
   }
-#else
-#pragma unroll
-  for (int r = 0; r < 16; ++r) t[r] *= dtanh(h[r]);
-#endif
 }
 
 __device__ inline void tanh16(f32x16& a) {

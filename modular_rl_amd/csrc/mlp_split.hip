@@ -3,7 +3,7 @@
 // The TRPO update spends ~90 % of its time in the ten Fisher products of CG
 // (trpo.py:45-58, 86-92: fvp = grad(grad(kl_ff) . v)).  On gfx950 the exact-f32 MFMA
 // (v_mfma_f32_32x32x2_f32) runs at 1/16 of the bf16 rate, and the f32 pair of kernels
-// (mlp_kernels.hip) sits at the f32 MFMA floor of the chip's power-held clock.  Here every
+// (mlp_rows_vjp.hip) sits at the f32 MFMA floor of the chip's power-held clock.  Here every
 // f32 MFMA operand v is split exactly into three bf16 parts, v = v0 + v1 + v2 (RNE
 // splits: v0 = bf16(v), v1 = bf16(v - v0), v2 = bf16(v - v0 - v1); each subtraction is
 // exact and the last remainder has at most 8 significant bits), and a product a.b is
@@ -16,12 +16,12 @@
 // rounding (tests/test_gpu_split.py) -- on the bf16 matrix cores.
 //
 // This file holds the Fisher product's JVP half (the tangent-forward rows and the KL
-// metric); its VJP half is mlp_vjp16_kernel's hybrid form (mlp_kernels.hip).  Layouts are
+// metric); its VJP half is mlp_vjp16_kernel's hybrid form (mlp_vjp16.hip).  Layouts are
 // those of the bf16 mode (bf16_frag.h, mlp_bf16.hip header): F tiles D[unit][row] chain
 // as B fragments; the split image is the bf16 image's f32 section (biases, VALU head)
 // followed by three copies of its forward bf16 section, part p at +p * PS.
 // The primal activations come from the f32 activation cache of the update's SURRGRAD
-// pass (mlp_kernels.hip cache layout = the F-tile register order), split on load.
+// pass (mlp_device.h cache layout = the F-tile register order), split on load.
 #include <math.h>
 #include <stdlib.h>
 
@@ -30,6 +30,7 @@
 #include "mlp_device.h"
 #include "rows_epilogue.h"
 #include "fvp_split_role.h"
+#include "mlp_host.h"
 
 namespace mrl {
 
@@ -208,28 +209,6 @@ int launch_rows_split(int epi, int sh, const RowsArgs& a, const BDims& b, const 
 
 using namespace mrl;
 
-static int check_desc_s(const mrl_mlp_desc* d) {
-  if (d == nullptr) return fail(E_ARG, "null mlp desc");
-  if (d->n_hidden != HID || d->n_layers != 2)
-    return fail(E_UNSUPPORTED, "only hid_sizes=[64,64] is implemented on the fused HIP path");
-  if (d->n_in < 1 || d->n_in > MAX_IN) return fail(E_UNSUPPORTED, "n_in must be in [1, 32]");
-  if (d->n_out < 1 || d->n_out > MAX_OUT) return fail(E_UNSUPPORTED, "n_out must be in [1, 8]");
-  if (d->head < 0 || d->head > 2) return fail(E_ARG, "bad head kind");
-  if (d->head == MRL_HEAD_LINEAR && d->n_out != 1) return fail(E_ARG, "linear head needs n_out=1");
-  return OK;
-}
-
-static int static_shape_split(const mrl_mlp_desc* d) {
-#ifdef MRL_NO_STATIC_SHAPES
-  (void)d;
-  return 0;
-#else
-  for (int i = 1; i < N_STATIC_SHAPES; ++i)
-    if (STATIC_SHAPES[i].O == d->n_in && STATIC_SHAPES[i].A == d->n_out && STATIC_SHAPES[i].head == d->head) return i;
-  return 0;
-#endif
-}
-
 // grid: two resident rounds (MRL_SPLIT_BLOCKS overrides)
 static int64_t split_rows_blocks(int64_t n) {
   static const int64_t env_cap = [] {
@@ -239,7 +218,7 @@ static int64_t split_rows_blocks(int64_t n) {
   // two resident rounds: 256 CUs x (4 waves per SIMD worth of blocks)
   const int64_t cap = env_cap > 0 ? env_cap : 2 * 256 * (4 * MRL_SPLIT_FVP_OCC / SPLIT_ROWS_WAVES > 0
                                                          ? 4 * MRL_SPLIT_FVP_OCC / SPLIT_ROWS_WAVES : 1);
-  int64_t g = ((n + 31) / 32 + SPLIT_ROWS_WAVES - 1) / SPLIT_ROWS_WAVES;
+  int64_t g = ceil_div(ceil_div(n, 32), SPLIT_ROWS_WAVES);
   if (g < 1) g = 1;
   return g > cap ? cap : g;
 }
@@ -247,15 +226,15 @@ static int64_t split_rows_blocks(int64_t n) {
 extern "C" {
 
 int64_t mrl_mlp_image_words_split(const mrl_mlp_desc* d) {
-  if (check_desc_s(d) != OK) return -1;
+  if (check_desc(d) != OK) return -1;
   return split_fwd_words(bf16_dims(d->n_in, d->n_out));
 }
 
 int mrl_mlp_pack_split(const mrl_mlp_desc* d, const float* theta, float* image, const int32_t* skip, void* stream) {
-  int rc = check_desc_s(d);
+  int rc = check_desc(d);
   if (rc) return rc;
   if (!theta || !image) return fail(E_ARG, "null pointer");
-  const MlpDims m = mlp_dims(d->n_in, d->n_out, d->head == MRL_HEAD_GAUSS);
+  const MlpDims m = dims_of(d);
   const BDims b = bf16_dims(d->n_in, d->n_out);
   const int items = b.fa0 + split_fw(b);
   hipLaunchKernelGGL(mlp_pack_split_kernel, dim3((items + 255) / 256), dim3(256), 0, (hipStream_t)stream, m, b, theta,
@@ -265,7 +244,7 @@ int mrl_mlp_pack_split(const mrl_mlp_desc* d, const float* theta, float* image, 
 
 int mrl_mlp_fvp_split(const mrl_mlp_desc* d, const float* theta, const float* image, const float* tangent,
                       const float* image_t, const mrl_rows_io* io, const int32_t* skip, void* stream) {
-  int rc = check_desc_s(d);
+  int rc = check_desc(d);
   if (rc) return rc;
   if (!io || !image || !image_t || !tangent || !io->x || !io->ghead) return fail(E_ARG, "null pointer");
   if (!io->act_cache || io->cache_mode != MRL_CACHE_READ)
@@ -275,7 +254,7 @@ int mrl_mlp_fvp_split(const mrl_mlp_desc* d, const float* theta, const float* im
   if (d->head == MRL_HEAD_GAUSS && !theta) return fail(E_ARG, "DiagGauss needs theta (logstd)");
   if (io->n <= 0) return OK;
   RowsArgs a{};
-  a.d = mlp_dims(d->n_in, d->n_out, d->head == MRL_HEAD_GAUSS);
+  a.d = dims_of(d);
   a.head = d->head;
   a.n_obs = d->n_in;
   a.gh = d->head == MRL_HEAD_GAUSS ? 2 * d->n_out : d->n_out;
@@ -292,7 +271,7 @@ int mrl_mlp_fvp_split(const mrl_mlp_desc* d, const float* theta, const float* im
   const size_t shm = (size_t)split_fwd_words(b) * 4 * 2;
   const dim3 grid(split_rows_blocks(io->n)), blk(SPLIT_ROWS_BLOCK);
   hipStream_t s = (hipStream_t)stream;
-  switch (static_shape_split(d)) {
+  switch (static_shape_of(d, false)) {
     case 1: hipLaunchKernelGGL((mlp_fvp_split_kernel<1>), grid, blk, shm, s, a, b, image, image_t, skip); break;
     case 2: hipLaunchKernelGGL((mlp_fvp_split_kernel<2>), grid, blk, shm, s, a, b, image, image_t, skip); break;
     default: hipLaunchKernelGGL((mlp_fvp_split_kernel<0>), grid, blk, shm, s, a, b, image, image_t, skip); break;

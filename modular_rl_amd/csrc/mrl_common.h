@@ -35,12 +35,7 @@ __host__ __device__ inline int cperm(int r, int h) { return (r & 3) + 8 * (r >> 
 // give each XCD a contiguous run of segments so a 128 B line shared by two
 // neighbouring segments is fetched into one L2 only.  Identity unless nb % 8 == 0.
 __device__ inline int64_t xcd_segment(int64_t b, int64_t nb) {
-#ifdef MRL_NO_XCD_SEGMENT  // ablation build (tools/build_ablate.sh)
-  (void)nb;
-  return b;
-#else
   return (nb % 8 == 0) ? (b % 8) * (nb / 8) + b / 8 : b;
-#endif
 }
 
 void set_error(const std::string& s);

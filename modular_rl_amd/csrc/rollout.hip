@@ -36,20 +36,13 @@ constexpr int MAXD = 16;  // obs dims + 1 (reward)
 // the SAME 16 envs: row g evaluates sincos of segment angle g and the contacts of
 // capsule g, and the rows exchange the results, so every row continues with the
 // identical state.  All lanes must be active.
-// the persistent kernel's capsule constants: 2 -- the row's own six, read from the LDS
-// table once per launch and held in registers; 1 -- read from the LDS table every substep;
-// 0 -- per-substep selects (A/B builds)
-#ifndef MRL_HP_CAP_LDS
-#define MRL_HP_CAP_LDS 2
-#endif
+// the persistent kernel's capsule constants: the row's own six, read from the LDS table
+// once per launch and held in registers (the other kernels select them per substep)
 struct HopperQuad {
   int g;
-  const double* capc;  // mode 2: the row's capsule {rad, mu, u0, u1, w0, w1}; mode 1: HP_CAP
-                       // in LDS ([field][k]); or null
+  const double* capc;  // the row's capsule {rad, mu, u0, u1, w0, w1}, or null
   __device__ CapsuleC capsule(int) const {
-    if (MRL_HP_CAP_LDS == 2 && capc != nullptr) return CapsuleC{capc[0], capc[1], capc[2], capc[3], capc[4], capc[5]};
-    if (MRL_HP_CAP_LDS == 1 && capc != nullptr)
-      return CapsuleC{capc[g], capc[4 + g], capc[8 + g], capc[12 + g], capc[16 + g], capc[20 + g]};
+    if (capc != nullptr) return CapsuleC{capc[0], capc[1], capc[2], capc[3], capc[4], capc[5]};
     return capsule_const(g);
   }
   __device__ void sincos4(const double* phi, double* s, double* c, double& so, double& co) const {
@@ -234,9 +227,6 @@ __device__ inline void tanh4(f32x4& a) {
 __device__ inline float bf16r(float x) { return (float)(__bf16)x; }
 template <bool BF>
 __device__ inline void tanh4r(f32x4& a) {
-#ifdef MRL_ABL_NOTANH  // diagnostic timing build only (results are wrong)
-  return;
-#endif
 #pragma unroll
   for (int r = 0; r < 4; r += 2) {
     const f32x2 t = tanh_fast2(f32x2{a[r], a[r + 1]});
@@ -249,9 +239,6 @@ __device__ inline void tanh4r(f32x4& a) {
 // BF (MRL_COMPUTE_BF16): x, h1, h2 rounded to bf16 (W0, W1 are rounded in the image),
 // the operands mlp_rows_bf16 multiplies -- the products and sums stay f32, so the prob
 // rows equal the update's bf16 forward up to f32 summation order.
-#ifndef MRL_FWD_WPF  // 1: a k-step's twelve split W1 fragments read from LDS ahead of its MFMAs
-#define MRL_FWD_WPF 1
-#endif
 template <int O, int A, bool BF, class XL>
 __device__ inline void forward16(const RWeights<O, A>& w, const XL& xl, int lane, float* z, int64_t* st = nullptr) {
   constexpr RDims R = RWeights<O, A>::R;
@@ -267,7 +254,7 @@ __device__ inline void forward16(const RWeights<O, A>& w, const XL& xl, int lane
 #pragma unroll
       for (int p = 0; p < 3; ++p) wf[mo][p] = w.w1s[(p * 8 + mo * 2 + s) * 64 + lane];
   };
-  if (MRL_FWD_WPF) load_wf(0);
+  load_wf(0);
   float xb[R.KS0p];
 #pragma unroll
   for (int ks = 0; ks < R.KS0p; ++ks) xb[ks] = ks < R.KS0 ? (BF ? bf16r(xl(4 * ks + g)) : xl(4 * ks + g)) : 0.f;
@@ -305,9 +292,8 @@ __device__ inline void forward16(const RWeights<O, A>& w, const XL& xl, int lane
 #pragma unroll
     for (int mo = 0; mo < 4; ++mo)
 #pragma unroll
-      for (int p = 0; p < 3; ++p)
-        wc[mo][p] = MRL_FWD_WPF ? wf[mo][p] : w.w1s[(p * 8 + mo * 2 + s) * 64 + lane];
-    if (MRL_FWD_WPF && s == 0) load_wf(1);
+      for (int p = 0; p < 3; ++p) wc[mo][p] = wf[mo][p];
+    if (s == 0) load_wf(1);
 #pragma unroll
     for (int mo = 0; mo < 4; ++mo) {
       const bf16x8 w0 = wc[mo][0], w1 = wc[mo][1], w2 = wc[mo][2];
@@ -1105,7 +1091,7 @@ __global__ __launch_bounds__(RB) void rollout_persistent_kernel(RollArgs a, cons
   }
   __syncthreads();
   publish_granules(gr, vals, nvalid, 0);  // gather step 0's partials
-  double capr[6];  // row g's capsule constants (MRL_HP_CAP_LDS 2)
+  double capr[6];  // row g's capsule constants
 #pragma unroll
   for (int f = 0; f < 6; ++f) capr[f] = hp_cap[4 * f + g];
 
@@ -1189,8 +1175,7 @@ __global__ __launch_bounds__(RB) void rollout_persistent_kernel(RollArgs a, cons
     // sample + env step on every row (split angle functions); row 0 stores
     double rew = 0.0;
     bool done = false;
-    sample_and_step<ENV, true, true>(a, row, z, sdv, zn, s, rew, done, valid && g == 0, g,
-                                     MRL_HP_CAP_LDS == 2 ? capr : hp_cap);
+    sample_and_step<ENV, true, true>(a, row, z, sdv, zn, s, rew, done, valid && g == 0, g, capr);
     PSTAMP(t, 4);
     // episode bookkeeping on every row, so the rows keep identical env state
     // (finish_env_step: gym TimeLimit => terminated; limit / horizon cut => not)
@@ -2044,7 +2029,7 @@ int64_t mrl_rollout_sync_bytes(const mrl_rollout_desc* d) {
 // the kernel boundary publishes them).  A kernel, not hipMemsetAsync: replayed from a
 // captured hipGraph after other work had been launched eagerly, the memset node of
 // ROCm 7.2 wrote a repeated 16-B pattern -- {int64 n, double 1/n}, bytes of a later
-// eager launch's arguments -- instead of zeros (tools/dbg/sync_probe.py).
+// eager launch's arguments -- instead of zeros.
 __global__ __launch_bounds__(256) void sync_clear_kernel(uint4* __restrict__ p, int64_t n16) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (int64_t)gridDim.x * 256)
     p[i] = make_uint4(0u, 0u, 0u, 0u);

@@ -1,4 +1,4 @@
-// Per-row epilogues shared by the fused 64-wide rows kernel (mlp_kernels.hip) and the
+// Per-row epilogues shared by the fused 64-wide rows kernel (mlp_rows_vjp.hip) and the
 // layered-path head kernel (gemm.hip): given the head pre-activation z (and its
 // tangent dz for the Fisher product) of one row, produce prob rows, the surrogate /
 // KL / entropy partial sums, the head-gradient row, or the VF squared error.

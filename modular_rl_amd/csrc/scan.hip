@@ -421,9 +421,6 @@ __global__ void vf_target_kernel(const float* __restrict__ ret, const float* __r
 
 // ------------------------------------------------------------------ CG (one workgroup)
 constexpr int CG_T = 1024;
-#ifndef MRL_CG_REG  // 1: the single-block CG update keeps its slices in registers (n <= 8192)
-#define MRL_CG_REG 1
-#endif
 
 // The sum of the block's CG_T values as the pairwise tree red[i] += red[i + o],
 // o = CG_T/2 .. 1, adds them (the tree every CG kernel's results are defined by), in
@@ -1142,7 +1139,7 @@ int mrl_cg_update(const float* fvp, double damping, double residual_tol, int64_t
     hipLaunchKernelGGL(cgm_xr_kernel, dim3(CGB), dim3(CGB_T), 0, s, fvp, damping, n, x, r, p, ax, state, flag);
     hipLaunchKernelGGL(cgm_p_kernel, dim3(CGB), dim3(CGB_T), 0, s, n, r, p, p32, state, flag);
     hipLaunchKernelGGL(cgm_final_kernel, dim3(1), dim3(CGB_T), 0, s, residual_tol, state, flag);
-  } else if (MRL_CG_REG && n <= 8 * CG_T) {
+  } else if (n <= 8 * CG_T) {  // the slices stay in registers
     hipLaunchKernelGGL(cg_update_reg_kernel<8>, dim3(1), dim3(CG_T), 0, s, fvp, damping, residual_tol, n, x, r, p,
                        p32, ax, state, flag);
   } else {
@@ -1156,7 +1153,7 @@ int mrl_cg_update_pack(const float* fvp, double damping, double residual_tol, in
                        double* p, float* p32, double* ax, double* state, int32_t* flag, const mrl_mlp_desc* d,
                        float* image_t, void* stream) {
   if (!fvp || !x || !r || !p || !p32 || !state || !flag || !d || !image_t) return fail(E_ARG, "null pointer");
-  if (!(MRL_CG_REG && n <= CG_SMALL_N && n <= 8 * CG_T))
+  if (!(n <= CG_SMALL_N && n <= 8 * CG_T))
     return fail(E_UNSUPPORTED, "mrl_cg_update_pack: the single-block register CG update only (n <= 8192)");
   const int64_t words = mrl_mlp_image_words_split(d);
   if (words < 0) return fail(E_UNSUPPORTED, "mrl_cg_update_pack: no split image for this net");
