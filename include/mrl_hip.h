@@ -519,6 +519,46 @@ int mrl_rollout_act_head_bf16(const mrl_rollout_desc* d, int32_t head, int32_t n
  * iteration counter (obs_T is never pushed: the horizon cuts the episode) */
 int mrl_rollout_finish(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, void* stream);
 
+/* ---------------------------------------------------------------- stand-alone env stepper
+ * The reference's loop `ob = env.reset(); ob, rew, done, _ = env.step(action)`
+ * (core.py:186-204) for E envs per call, with the caller's own actions: the same dynamics,
+ * state buffers and reset streams as the rollout, no policy and no filter.  From the desc
+ * they read env_id, n_envs, timestep_limit (<= 0: none), env_offset and seed; from the
+ * bufs env_state and env_int only -- a Collector's envs and a stand-alone handle are the
+ * same object.  Observations are the raw fp64 rows; mrl_obfilter_update_apply is the
+ * ZFilter over them. */
+typedef struct {
+  const void* act;       /* step: [E] int32 (discrete) | [E, act_dim] float            */
+  const uint8_t* mask;   /* reset: NULL = every env, else [E], non-zero = reset        */
+  double* obs;           /* [E, obs_dim] row-major raw observation                     */
+  double* rew;           /* step: [E]                                                  */
+  uint8_t* flags;        /* step: [E] bit0 episode ended, bit1 terminated              */
+  int32_t* ep_t;         /* step: [E] index of the step inside its episode             */
+  double* final_obs;     /* step, optional: [E, obs_dim], written where bit0 is set    */
+} mrl_env_io;
+
+/* reset the envs the mask selects (reset noise: Philox (seed, domain 1, env_offset + e,
+ * episodes started), the rollout's stream) and write their observation rows; the other
+ * envs and their rows are untouched */
+int mrl_env_reset(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, const mrl_env_io* io, void* stream);
+/* one step of every env with the caller's action.  bit1 (terminated) = env done or its
+ * TimeLimit; bit0 (ended) = terminated or ep_t + 1 >= timestep_limit.  auto_reset != 0: an
+ * ended env is reset in the same call, its obs row is the new episode's first observation
+ * and final_obs (if given) the observation that ended the old one.  auto_reset == 0:
+ * nothing resets; stepping an ended env goes on integrating and counting. */
+int mrl_env_step(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, const mrl_env_io* io, int32_t auto_reset,
+                 void* stream);
+/* ZFilter (filters.py:17-40) over a batch x [n_rows, dim] of fp64 rows: update != 0 merges
+ * the batch into the running stat (per-block partials over 64 rows, batch in block order,
+ * one Chan merge -- the rollout's arithmetic, bit for bit), then out [n_rows, dim] (fp32)
+ * = clip((x - M) / (sqrt(var) + 1e-8), +-clip).  state: the rollout's filter layout
+ * [n_obs, n_rew, M[dim+1], S[dim+1]] (mrl_filter_doubles), one copy updated in place;
+ * n_obs and the first dim columns are read and written.  workspace: device memory of
+ * mrl_obfilter_workspace_bytes(n_rows, dim) bytes. */
+int64_t mrl_obfilter_workspace_bytes(int64_t n_rows, int32_t dim);
+int mrl_obfilter_update_apply(double* state, int32_t dim, const double* x, int64_t n_rows, int32_t update,
+                              double clip, float* out, void* workspace, void* stream);
+
 /* ---------------------------------------------------------------- streams
  * CU-masked HIP streams for the iteration pipeline (the rollout of iteration k+1
  * and the VF fit of iteration k run at once on disjoint CU sets).  No reference

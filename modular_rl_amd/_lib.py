@@ -74,6 +74,10 @@ class RolloutBufs(ctypes.Structure):
                 ("stamps", vp), ("raw_obs", vp), ("obs_bf16", vp)]
 
 
+class EnvIO(ctypes.Structure):
+    _fields_ = [("act", vp), ("mask", vp), ("obs", vp), ("rew", vp), ("flags", vp), ("ep_t", vp), ("final_obs", vp)]
+
+
 # name -> (restype, argtypes); every symbol include/mrl_hip.h declares
 SIGNATURES = {
     "mrl_last_error": (ctypes.c_char_p, []),
@@ -162,6 +166,10 @@ SIGNATURES = {
     "mrl_rollout_act": (i32, [vp, i32, i32, vp, vp, vp, i32, vp]),
     "mrl_rollout_act_head": (i32, [vp, i32, i32, vp, i32, vp, vp, vp, vp, i32, vp]),
     "mrl_rollout_act_head_bf16": (i32, [vp, i32, i32, vp, i32, vp, vp, vp, vp, i32, vp]),
+    "mrl_env_reset": (i32, [vp, vp, vp, vp]),
+    "mrl_env_step": (i32, [vp, vp, vp, i32, vp]),
+    "mrl_obfilter_workspace_bytes": (i64, [i64, i32]),
+    "mrl_obfilter_update_apply": (i32, [vp, i32, vp, i64, i32, f64, vp, vp, vp]),
 }
 
 _lib = None

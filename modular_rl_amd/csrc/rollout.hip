@@ -1239,6 +1239,47 @@ constexpr int MAXD_L = 384;  // obs dims + 1 on the layered path
 // makes every per-column loop long, so no block walks all columns.
 constexpr int LCOLS = 32;
 
+// two-pass (mean, M2) of one column over a block's nvalid rows, for the 256 threads of an
+// (env block, 32-column chunk) block: thread (c = tid & 31, g = tid >> 5) takes rows g, g + 8,
+// ... of column c through load(row), loaded once, all issued together, for both passes; the
+// sums stay in row order.  Shared by the layered rollout's partials and the stand-alone
+// filter, which must agree bit for bit.  The results are valid in the threads with g == 0.
+template <class Load>
+__device__ inline void col_partial(Load load, int nvalid, bool kin, double (*red)[LCOLS], int c, int g, double& mean,
+                                   double& m2out) {
+  constexpr int PR = ENVS_PER_BLOCK / 8;
+  double cv[PR];
+#pragma unroll
+  for (int q = 0; q < PR; ++q) cv[q] = load(min(g + 8 * q, max(nvalid - 1, 0)));  // clamped: in the column
+  double sm = 0.0;
+  if (kin)
+#pragma unroll
+    for (int q = 0; q < PR; ++q)
+      if (g + 8 * q < nvalid) sm += cv[q];
+  red[g][c] = sm;
+  __syncthreads();
+  double tot = 0.0;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) tot += red[q][c];
+  mean = nvalid > 0 ? div_count(tot, (double)nvalid) : 0.0;
+  __syncthreads();
+  double m2 = 0.0;
+  if (kin)
+#pragma unroll
+    for (int q = 0; q < PR; ++q)
+      if (g + 8 * q < nvalid) {
+        const double dv = cv[q] - mean;
+        m2 += dv * dv;
+      }
+  red[g][c] = m2;
+  __syncthreads();
+  double t2 = 0.0;
+  if (g == 0 && kin)
+#pragma unroll
+    for (int q = 0; q < 8; ++q) t2 += red[q][c];
+  m2out = t2;
+}
+
 // per-(env block, column chunk) two-pass partial of the SoA rows raw[k][e0 .. e0+nvalid):
 // column k = 32*blockIdx.y + (tid & 31); 8 thread groups stride the envs.
 __global__ __launch_bounds__(RB) void lrollout_partials_kernel(RollArgs a, int D, int rec_parity, int with_rew) {
@@ -1250,38 +1291,9 @@ __global__ __launch_bounds__(RB) void lrollout_partials_kernel(RollArgs a, int D
   const int k = blockIdx.y * LCOLS + c;
   double* r = a.b.records + (int64_t)rec_parity * a.nb * a.RS + (int64_t)blockIdx.x * a.RS;
   const double* col = a.b.raw_obs + (int64_t)(k < D ? k : 0) * E + e0;
-  // this thread's values (rows g, g + 8, ...) loaded once, all issued together, for both
-  // passes; the sums stay in row order
-  constexpr int PR = ENVS_PER_BLOCK / 8;
-  double cv[PR];
-#pragma unroll
-  for (int q = 0; q < PR; ++q) cv[q] = col[min(g + 8 * q, max(nvalid - 1, 0))];  // clamped: in the column
-  double sm = 0.0;
-  if (k < D)
-#pragma unroll
-    for (int q = 0; q < PR; ++q)
-      if (g + 8 * q < nvalid) sm += cv[q];
-  red[g][c] = sm;
-  __syncthreads();
-  double tot = 0.0;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) tot += red[q][c];
-  const double mean = nvalid > 0 ? div_count(tot, (double)nvalid) : 0.0;
-  __syncthreads();
-  double m2 = 0.0;
-  if (k < D)
-#pragma unroll
-    for (int q = 0; q < PR; ++q)
-      if (g + 8 * q < nvalid) {
-        const double dv = cv[q] - mean;
-        m2 += dv * dv;
-      }
-  red[g][c] = m2;
-  __syncthreads();
+  double mean, t2;
+  col_partial([&](int row) { return col[row]; }, nvalid, k < D, red, c, g, mean, t2);
   if (g == 0 && k < D) {
-    double t2 = 0.0;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) t2 += red[q][c];
     r[2 + k] = mean;
     r[2 + D + k] = t2;
   }
@@ -1306,6 +1318,83 @@ __global__ __launch_bounds__(RB) void lrollout_reset_kernel(RollArgs a) {
     EC::obs_out(s, [&](int k, double v) { raw[(int64_t)k * E + e] = v; });
     raw[(int64_t)O * E + e] = 0.0;
   }
+}
+
+// column k of the batch records (block order, two passes: n, mean = sum n_b m_b / n,
+// M2 = sum M2_b + n_b (m_b - mean)^2 -- oracle/rollout_np.py _batch) Chan-merged into the
+// running stat fs_in -> (n, M, S).  Shared by lrollout_obs_kernel and the stand-alone filter.
+__device__ inline void merge_records_column(const double* rec, int nb, int RS, int D, int k, bool isr,
+                                            const double* fs_in, double& n, double& M, double& S) {
+  // the block records in chunks of LREC: every load of a chunk issued before the
+  // chunk's sums (the sums themselves stay sequential in block order, as the oracle's);
+  // one dependent global load per block per pass had made this launch ~14 us of waiting
+  constexpr int LREC = 16;
+  double bn = 0.0, sm = 0.0, bm = 0.0, bs = 0.0;
+  // the filter's M2 terms and the fs_in state loaded with the first chunk (one record
+  // round trip when nb <= LREC: the second pass reuses the first's loads)
+  double rn1[LREC], rm1[LREC], rs1[LREC];
+  const double n0 = fs_in[isr ? 1 : 0], M0 = fs_in[2 + k], S0 = fs_in[2 + D + k];
+  if (nb <= LREC) {
+#pragma unroll
+    for (int q = 0; q < LREC; ++q) {
+      const double* r = rec + (int64_t)min(q, nb - 1) * RS;
+      rn1[q] = r[isr ? 1 : 0];
+      rm1[q] = r[2 + k];
+      rs1[q] = r[2 + D + k];
+    }
+#pragma unroll
+    for (int q = 0; q < LREC; ++q)
+      if (q < nb) {
+        bn += rn1[q];
+        sm += rn1[q] * rm1[q];
+      }
+    if (bn > 0.0) {
+      bm = sm / bn;
+#pragma unroll
+      for (int q = 0; q < LREC; ++q)
+        if (q < nb && rn1[q] > 0.0) {
+          const double dm = rm1[q] - bm;
+          bs += rs1[q] + rn1[q] * dm * dm;
+        }
+    }
+  } else {
+    for (int b0 = 0; b0 < nb; b0 += LREC) {
+      double rn[LREC], rm[LREC];
+#pragma unroll
+      for (int q = 0; q < LREC; ++q) {
+        const double* r = rec + (int64_t)min(b0 + q, nb - 1) * RS;
+        rn[q] = r[isr ? 1 : 0];
+        rm[q] = r[2 + k];
+      }
+#pragma unroll
+      for (int q = 0; q < LREC; ++q)
+        if (b0 + q < nb) {
+          bn += rn[q];
+          sm += rn[q] * rm[q];
+        }
+    }
+    if (bn > 0.0) {
+      bm = sm / bn;
+      for (int b0 = 0; b0 < nb; b0 += LREC) {
+        double rn[LREC], rm[LREC], rs[LREC];
+#pragma unroll
+        for (int q = 0; q < LREC; ++q) {
+          const double* r = rec + (int64_t)min(b0 + q, nb - 1) * RS;
+          rn[q] = r[isr ? 1 : 0];
+          rm[q] = r[2 + k];
+          rs[q] = r[2 + D + k];
+        }
+#pragma unroll
+        for (int q = 0; q < LREC; ++q)
+          if (b0 + q < nb && rn[q] > 0.0) {
+            const double dm = rm[q] - bm;
+            bs += rs[q] + rn[q] * dm * dm;
+          }
+      }
+    }
+  }
+  n = n0, M = M0, S = S0;
+  chan_merge(n, M, S, bn, bm, bs);
 }
 
 // merge of the batch records (block order, two passes: n, mean = sum n_b m_b / n,
@@ -1338,76 +1427,8 @@ __global__ __launch_bounds__(RB) void lrollout_obs_kernel(RollArgs a, int t) {
   if (threadIdx.x < LCOLS && kbase + (int)threadIdx.x < D) {
     const int k = kbase + threadIdx.x;
     const bool isr = (k == O);
-    // the block records in chunks of LREC: every load of a chunk issued before the
-    // chunk's sums (the sums themselves stay sequential in block order, as the oracle's);
-    // one dependent global load per block per pass had made this launch ~14 us of waiting
-    constexpr int LREC = 16;
-    double bn = 0.0, sm = 0.0, bm = 0.0, bs = 0.0;
-    // the filter's M2 terms and the fs_in state loaded with the first chunk (one record
-    // round trip when nb <= LREC: the second pass reuses the first's loads)
-    double rn1[LREC], rm1[LREC], rs1[LREC];
-    const double n0 = fs_in[isr ? 1 : 0], M0 = fs_in[2 + k], S0 = fs_in[2 + D + k];
-    if (a.nb <= LREC) {
-#pragma unroll
-      for (int q = 0; q < LREC; ++q) {
-        const double* r = rec + (int64_t)min(q, a.nb - 1) * a.RS;
-        rn1[q] = r[isr ? 1 : 0];
-        rm1[q] = r[2 + k];
-        rs1[q] = r[2 + D + k];
-      }
-#pragma unroll
-      for (int q = 0; q < LREC; ++q)
-        if (q < a.nb) {
-          bn += rn1[q];
-          sm += rn1[q] * rm1[q];
-        }
-      if (bn > 0.0) {
-        bm = sm / bn;
-#pragma unroll
-        for (int q = 0; q < LREC; ++q)
-          if (q < a.nb && rn1[q] > 0.0) {
-            const double dm = rm1[q] - bm;
-            bs += rs1[q] + rn1[q] * dm * dm;
-          }
-      }
-    } else {
-      for (int b0 = 0; b0 < a.nb; b0 += LREC) {
-        double rn[LREC], rm[LREC];
-#pragma unroll
-        for (int q = 0; q < LREC; ++q) {
-          const double* r = rec + (int64_t)min(b0 + q, a.nb - 1) * a.RS;
-          rn[q] = r[isr ? 1 : 0];
-          rm[q] = r[2 + k];
-        }
-#pragma unroll
-        for (int q = 0; q < LREC; ++q)
-          if (b0 + q < a.nb) {
-            bn += rn[q];
-            sm += rn[q] * rm[q];
-          }
-      }
-      if (bn > 0.0) {
-        bm = sm / bn;
-        for (int b0 = 0; b0 < a.nb; b0 += LREC) {
-          double rn[LREC], rm[LREC], rs[LREC];
-#pragma unroll
-          for (int q = 0; q < LREC; ++q) {
-            const double* r = rec + (int64_t)min(b0 + q, a.nb - 1) * a.RS;
-            rn[q] = r[isr ? 1 : 0];
-            rm[q] = r[2 + k];
-            rs[q] = r[2 + D + k];
-          }
-#pragma unroll
-          for (int q = 0; q < LREC; ++q)
-            if (b0 + q < a.nb && rn[q] > 0.0) {
-              const double dm = rm[q] - bm;
-              bs += rs[q] + rn[q] * dm * dm;
-            }
-        }
-      }
-    }
-    double n = n0, M = M0, S = S0;
-    chan_merge(n, M, S, bn, bm, bs);
+    double n, M, S;
+    merge_records_column(rec, a.nb, a.RS, D, k, isr, fs_in, n, M, S);
     if (blockIdx.x == 0) {
       if (k == 0) fs_out[0] = n;
       if (isr) fs_out[1] = n;
@@ -1777,6 +1798,243 @@ static size_t hm_lds_bytes(int wpb, int n_envs) {
   return wpb == 1 ? hm_lds_pad(n_envs) : (size_t)wpb * sizeof(hm::Wave);
 }
 
+// ------------------------------------------------------------------ stand-alone env stepper
+// The envs without a policy: mrl_env_reset / mrl_env_step drive the same state buffers
+// (env_state, env_int) with the caller's actions, one launch per call.  Same device
+// functions as the rollout kernels; raw fp64 observation rows [E, obs_dim], row-major.
+// Thread per env with one wave per block (the per-env step is a latency chain: the waves
+// spread over the CUs); Humanoid wave per env like hm_reset_kernel / hm_act_kernel.
+template <int ENV>
+__global__ __launch_bounds__(64) void env_reset_kernel(RollArgs a, mrl_env_io io) {
+  using EC = EnvC<ENV>;
+  constexpr int O = EC::OBS;
+  const int E = a.d.n_envs;
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= E || (io.mask != nullptr && io.mask[e] == 0)) return;
+  double s[EC::NS];
+  reset_env<ENV>(a, e, s);
+#pragma unroll
+  for (int i = 0; i < EC::NS; ++i) a.b.env_state[(int64_t)i * E + e] = s[i];
+  double* orow = io.obs + (int64_t)e * O;
+  EC::obs_out(s, [&](int k, double v) { orow[k] = v; });
+}
+
+// episode bookkeeping of finish_env_step without the horizon: TimeLimit => terminated,
+// the caller's limit => ended, not terminated
+template <int ENV>
+__device__ inline void env_step_flags(const RollArgs& a, int ept, bool done, bool& term, bool& last) {
+  term = done || (ept + 1 >= EnvC<ENV>::MAX_STEPS);
+  last = term || (a.d.timestep_limit > 0 && ept + 1 >= a.d.timestep_limit);
+}
+
+template <int ENV>
+__global__ __launch_bounds__(64) void env_step_kernel(RollArgs a, mrl_env_io io, int auto_reset) {
+  using EC = EnvC<ENV>;
+  constexpr int O = EC::OBS, NS = EC::NS, A = EC::ACT;
+  const int E = a.d.n_envs;
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= E) return;
+  double s[NS];
+#pragma unroll
+  for (int i = 0; i < NS; ++i) s[i] = a.b.env_state[(int64_t)i * E + e];
+  double rew = 0.0;
+  bool done = false;
+  if constexpr (EC::DISCRETE) {
+    EC::step_disc(s, reinterpret_cast<const int32_t*>(io.act)[e], rew, done);
+  } else {
+    float av[A];
+#pragma unroll
+    for (int q = 0; q < A; ++q) av[q] = reinterpret_cast<const float*>(io.act)[(int64_t)e * A + q];
+    EC::step_cont(s, av, rew, done);
+  }
+  const int ept = a.b.env_int[e];
+  bool term, last;
+  env_step_flags<ENV>(a, ept, done, term, last);
+  io.ep_t[e] = ept;
+  io.rew[e] = rew;
+  io.flags[e] = (uint8_t)((last ? 1 : 0) | (term ? 2 : 0));
+  if (last && io.final_obs != nullptr) {
+    double* frow = io.final_obs + (int64_t)e * O;
+    EC::obs_out(s, [&](int k, double v) { frow[k] = v; });
+  }
+  if (last && auto_reset) reset_env<ENV>(a, e, s);
+  else a.b.env_int[e] = ept + 1;
+#pragma unroll
+  for (int i = 0; i < NS; ++i) a.b.env_state[(int64_t)i * E + e] = s[i];
+  double* orow = io.obs + (int64_t)e * O;
+  EC::obs_out(s, [&](int k, double v) { orow[k] = v; });
+}
+
+template <int WPB>
+__global__ __launch_bounds__(64 * WPB) void hm_env_reset_kernel(RollArgs a, mrl_env_io io) {
+  __shared__ hm::Shared S;
+  int e, lane;
+  hm::Wave& W = hm_block<WPB>(e, lane);
+  const int E = a.d.n_envs;
+  hm_load_tables<WPB>(S, lane);
+  if (e >= E || (io.mask != nullptr && io.mask[e] == 0)) return;  // after the tables' barrier
+  const uint32_t w = (uint32_t)a.b.env_int[E + e];
+  hm::reset(W, lane, a.d.seed, (uint32_t)(a.d.env_offset + e), (uint64_t)w);
+  hm::forward(W, S, lane);
+  double* orow = io.obs + (int64_t)e * HM_OBS;
+  hm::observation(W, S, lane, [&](int k, double v) { orow[k] = v; });
+  if (lane < HM_NS) a.b.env_state[(int64_t)lane * E + e] = W.s[lane];
+  hm::save_kcache(W, a.b.env_state + (int64_t)HM_NS * E + (int64_t)e * HM_KCACHE, lane);
+  if (lane == 0) {
+    a.b.env_int[E + e] = (int32_t)(w + 1);
+    a.b.env_int[e] = 0;
+  }
+}
+
+// hm_act_kernel with the caller's ctrl in place of the sampled one
+template <int WPB>
+__global__ __launch_bounds__(64 * WPB) void hm_env_step_kernel(RollArgs a, mrl_env_io io, int auto_reset) {
+  __shared__ hm::Shared S;
+  int e, lane;
+  hm::Wave& W = hm_block<WPB>(e, lane);
+  constexpr int A = HM_ACT;
+  const int E = a.d.n_envs;
+  const bool live = e < E;
+  const int ec = live ? e : E - 1;  // a block's waves past E load a valid env, store nothing
+  double* const kc = a.b.env_state + (int64_t)HM_NS * E + (int64_t)ec * HM_KCACHE;
+  hm_load_tables<WPB>(S, lane);
+  if (!live) return;  // after the tables' barrier
+  if (lane < HM_NS) W.s[lane] = a.b.env_state[(int64_t)lane * E + e];
+  hm::load_kcache(W, kc, lane);
+  WAVE_SYNC();
+  if (lane < A) W.s[HM_NQ + HM_NV + lane] = (double)reinterpret_cast<const float*>(io.act)[(int64_t)e * A + lane];
+  WAVE_SYNC();
+  // one forward and one observation site, as in hm_act_kernel: passes 0..FRAME_SKIP-1 are
+  // the substeps, pass FRAME_SKIP observes the new state (into final_obs when the env is
+  // reset in this call), pass FRAME_SKIP + 1 the reset one
+  double x_before = 0.0, rew = 0.0;
+  for (int pass = 0;; ++pass) {
+    if (pass > 0) hm::forward(W, S, lane);  // pass 0: the kinematics cache
+    if (pass < hm::FRAME_SKIP) {
+      if (pass == 0) x_before = W.com[0];
+      hm::accelerations(W, S, lane);
+      hm::integrate(W, lane);
+      continue;
+    }
+    double* orow = io.obs + (int64_t)e * HM_OBS;
+    double* orow2 = nullptr;
+    bool again = false;
+    if (pass == hm::FRAME_SKIP) {
+      bool done, term, last;
+      hm::reward_done(W, lane, x_before, rew, done);
+      const int ept = a.b.env_int[e];
+      env_step_flags<MRL_ENV_HUMANOID>(a, ept, done, term, last);
+      if (lane == 0) {
+        io.ep_t[e] = ept;
+        io.rew[e] = rew;
+        io.flags[e] = (uint8_t)((last ? 1 : 0) | (term ? 2 : 0));
+      }
+      again = last && auto_reset;
+      if (!again && lane == 0) a.b.env_int[e] = ept + 1;
+      double* frow = io.final_obs != nullptr ? io.final_obs + (int64_t)e * HM_OBS : nullptr;
+      if (again) orow = frow;  // the obs row waits for the reset state
+      else if (last) orow2 = frow;
+    }
+    if (orow != nullptr)
+      hm::observation(W, S, lane, [&](int k, double v) {
+        orow[k] = v;
+        if (orow2 != nullptr) orow2[k] = v;
+      });
+    if (!again) break;
+    const uint32_t w = (uint32_t)a.b.env_int[E + e];
+    hm::reset(W, lane, a.d.seed, (uint32_t)(a.d.env_offset + e), (uint64_t)w);
+    if (lane == 0) {
+      a.b.env_int[E + e] = (int32_t)(w + 1);
+      a.b.env_int[e] = 0;
+    }
+  }
+  if (lane < HM_NS) a.b.env_state[(int64_t)lane * E + e] = W.s[lane];
+  hm::save_kcache(W, kc, lane);  // W holds forward() of the state just stored
+}
+
+// ------------------------------------------------------------------ stand-alone obs filter
+// ZFilter (filters.py:17-40) over a batch of row-major fp64 rows x[n_rows, dim], in the
+// layered rollout's arithmetic (col_partial, merge_records_column, lrollout_obs_kernel's
+// normalisation), so the same rows in the same order give the same bits as mrl_rollout_obs.
+// state = [n_obs, n_rew, M[dim+1], S[dim+1]], one copy updated in place: the merge
+// (obfilter_merge_kernel, one thread per column) writes its own M, S and stages n, the
+// mean and the denominator of every column in the workspace; the apply kernel reads only
+// the staged values and stores n, so no block reads what another writes.
+// workspace: records [nb][2 + 2 (dim + 1)] | mean [dim] | den [dim] | n
+__global__ __launch_bounds__(RB) void obfilter_partials_kernel(const double* __restrict__ x, int64_t n_rows, int dim,
+                                                               double* __restrict__ rec) {
+  __shared__ double red[8][LCOLS];
+  const int64_t r0 = (int64_t)blockIdx.x * ENVS_PER_BLOCK;
+  const int nvalid = (int)(n_rows - r0 < ENVS_PER_BLOCK ? n_rows - r0 : ENVS_PER_BLOCK);
+  const int c = threadIdx.x & (LCOLS - 1), g = threadIdx.x >> 5;
+  const int k = blockIdx.y * LCOLS + c;
+  const int D = dim + 1, RS = 2 + 2 * D;  // the rollout's record layout (the reward column unused)
+  double* r = rec + (int64_t)blockIdx.x * RS;
+  const double* col = x + r0 * dim + (k < dim ? k : 0);
+  double mean, t2;
+  col_partial([&](int row) { return col[(int64_t)row * dim]; }, nvalid, k < dim, red, c, g, mean, t2);
+  if (g == 0 && k < dim) {
+    r[2 + k] = mean;
+    r[2 + D + k] = t2;
+  }
+  if (blockIdx.y == 0 && threadIdx.x == 0) {
+    r[0] = (double)nvalid;
+    r[1] = 0.0;
+  }
+}
+
+__global__ __launch_bounds__(LCOLS) void obfilter_merge_kernel(double* __restrict__ state, int dim, int nb, int update,
+                                                               double* __restrict__ ws) {
+  const int k = blockIdx.x * LCOLS + threadIdx.x;
+  if (k >= dim) return;
+  const int D = dim + 1, RS = 2 + 2 * D;
+  double* stage = ws + (int64_t)nb * RS;
+  double n, M, S;
+  if (update) {
+    merge_records_column(ws, nb, RS, D, k, false, state, n, M, S);
+  } else {
+    n = state[0];
+    M = state[2 + k];
+    S = state[2 + D + k];
+  }
+  const double var = n > 1.0 ? S / (n - 1.0) : M * M;  // running_stat.py:27
+  stage[k] = M;
+  stage[dim + k] = sqrt(var) + 1e-8;
+  if (k == 0) stage[2 * dim] = n;
+  if (update) {
+    state[2 + k] = M;
+    state[2 + D + k] = S;
+  }
+}
+
+__global__ __launch_bounds__(RB) void obfilter_apply_kernel(const double* __restrict__ x, int64_t n_rows, int dim,
+                                                            double clip, const double* __restrict__ stage,
+                                                            float* __restrict__ out, double* n_out) {
+  __shared__ double fmean[LCOLS], fden[LCOLS];
+  const int kbase = blockIdx.y * LCOLS;
+  if (threadIdx.x < LCOLS && kbase + (int)threadIdx.x < dim) {
+    fmean[threadIdx.x] = stage[kbase + threadIdx.x];
+    fden[threadIdx.x] = stage[dim + kbase + threadIdx.x];
+  }
+  if (n_out != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *n_out = stage[2 * dim];
+  __syncthreads();
+  // thread (row = tid / 4 of the block's 64, 8 consecutive columns of the chunk)
+  constexpr int G = RB / ENVS_PER_BLOCK, CPT = LCOLS / G;
+  const int64_t row = (int64_t)blockIdx.x * ENVS_PER_BLOCK + threadIdx.x / G;
+  if (row >= n_rows) return;
+#pragma unroll
+  for (int q = 0; q < CPT; ++q) {
+    const int kl = (threadIdx.x % G) * CPT + q, k = kbase + kl;
+    if (k < dim) {
+      double v = x[row * dim + k];
+      v = v - fmean[kl];
+      v = v / fden[kl];
+      v = v < -clip ? -clip : (v > clip ? clip : v);
+      out[row * dim + k] = (float)v;
+    }
+  }
+}
+
 __global__ void rollout_finish_kernel(RollArgs a, int O) {
   const int D = O + 1, T = a.d.horizon;
   const double* fs_in = a.b.filter_state + (T & 1) * a.FS;
@@ -2137,6 +2395,96 @@ int mrl_rollout_finish(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, voi
   RollArgs a = make_args(d, b);
   hipLaunchKernelGGL(rollout_finish_kernel, dim3(1), dim3(RB), 0, (hipStream_t)stream, a, env_info(d->env_id).obs);
   return hip_check(hipGetLastError(), "mrl_rollout_finish");
+}
+
+// the stand-alone stepper's arguments: checked before any HIP call
+static int check_env(const char* who, const mrl_rollout_desc* d, const mrl_rollout_bufs* b, const mrl_env_io* io) {
+  const char* what = nullptr;
+  if (!d) what = "null desc";
+  else if (!b) what = "null bufs";
+  else if (!io) what = "null io";
+  else if (d->env_id != MRL_ENV_CARTPOLE && d->env_id != MRL_ENV_HOPPER && d->env_id != MRL_ENV_HUMANOID)
+    what = "desc.env_id: unknown env";
+  else if (d->n_envs <= 0) what = "desc.n_envs <= 0";
+  else if (!b->env_state) what = "null bufs.env_state";
+  else if (!b->env_int) what = "null bufs.env_int";
+  else if (!io->obs) what = "null io.obs";
+  if (!what) return OK;
+  return fail(E_ARG, std::string(who) + ": " + what);
+}
+
+int mrl_env_reset(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, const mrl_env_io* io, void* stream) {
+  int rc = check_env("mrl_env_reset", d, b, io);
+  if (rc) return rc;
+  RollArgs a = make_args(d, b);
+  const dim3 genv((d->n_envs + 63) / 64);
+  if (d->env_id == MRL_ENV_HUMANOID) {
+    const int wpb = hm_wpb();
+    const dim3 gb((d->n_envs + wpb - 1) / wpb), bb(64 * wpb);
+    const size_t lds = wpb == 1 ? 0 : (size_t)wpb * sizeof(hm::Wave);
+    if (wpb == 4) hipLaunchKernelGGL(hm_env_reset_kernel<4>, gb, bb, lds, (hipStream_t)stream, a, *io);
+    else hipLaunchKernelGGL(hm_env_reset_kernel<1>, gb, bb, lds, (hipStream_t)stream, a, *io);
+  } else if (d->env_id == MRL_ENV_CARTPOLE)
+    hipLaunchKernelGGL(env_reset_kernel<MRL_ENV_CARTPOLE>, genv, dim3(64), 0, (hipStream_t)stream, a, *io);
+  else
+    hipLaunchKernelGGL(env_reset_kernel<MRL_ENV_HOPPER>, genv, dim3(64), 0, (hipStream_t)stream, a, *io);
+  return hip_check(hipGetLastError(), "mrl_env_reset");
+}
+
+int mrl_env_step(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, const mrl_env_io* io, int32_t auto_reset,
+                 void* stream) {
+  int rc = check_env("mrl_env_step", d, b, io);
+  if (rc) return rc;
+  if (!io->act) return fail(E_ARG, "mrl_env_step: null io.act");
+  if (!io->rew) return fail(E_ARG, "mrl_env_step: null io.rew");
+  if (!io->flags) return fail(E_ARG, "mrl_env_step: null io.flags");
+  if (!io->ep_t) return fail(E_ARG, "mrl_env_step: null io.ep_t");
+  RollArgs a = make_args(d, b);
+  const int ar = auto_reset != 0;
+  const dim3 genv((d->n_envs + 63) / 64);
+  if (d->env_id == MRL_ENV_HUMANOID) {
+    const int wpb = hm_wpb();
+    const dim3 gb((d->n_envs + wpb - 1) / wpb), bb(64 * wpb);
+    const size_t lds = hm_lds_bytes(wpb, d->n_envs);
+    if (wpb == 4) hipLaunchKernelGGL(hm_env_step_kernel<4>, gb, bb, lds, (hipStream_t)stream, a, *io, ar);
+    else hipLaunchKernelGGL(hm_env_step_kernel<1>, gb, bb, lds, (hipStream_t)stream, a, *io, ar);
+  } else if (d->env_id == MRL_ENV_CARTPOLE)
+    hipLaunchKernelGGL(env_step_kernel<MRL_ENV_CARTPOLE>, genv, dim3(64), 0, (hipStream_t)stream, a, *io, ar);
+  else
+    hipLaunchKernelGGL(env_step_kernel<MRL_ENV_HOPPER>, genv, dim3(64), 0, (hipStream_t)stream, a, *io, ar);
+  return hip_check(hipGetLastError(), "mrl_env_step");
+}
+
+// rows per launch dimension: blocks of 64 rows in grid.x
+static constexpr int64_t OBF_MAX_ROWS = (int64_t)0x7fffffff * 32;
+static constexpr int32_t OBF_MAX_DIM = 65535 * LCOLS;
+
+int64_t mrl_obfilter_workspace_bytes(int64_t n_rows, int32_t dim) {
+  if (n_rows <= 0 || n_rows > OBF_MAX_ROWS || dim <= 0 || dim > OBF_MAX_DIM) return -1;
+  const int64_t nb = (n_rows + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
+  return (nb * (2 + 2 * ((int64_t)dim + 1)) + 2 * (int64_t)dim + 1) * (int64_t)sizeof(double);
+}
+
+int mrl_obfilter_update_apply(double* state, int32_t dim, const double* x, int64_t n_rows, int32_t update,
+                              double clip, float* out, void* workspace, void* stream) {
+  if (!state) return fail(E_ARG, "mrl_obfilter_update_apply: null state");
+  if (dim <= 0 || dim > OBF_MAX_DIM) return fail(E_ARG, "mrl_obfilter_update_apply: dim out of range");
+  if (n_rows <= 0 || n_rows > OBF_MAX_ROWS) return fail(E_ARG, "mrl_obfilter_update_apply: n_rows out of range");
+  if (!x) return fail(E_ARG, "mrl_obfilter_update_apply: null x");
+  if (!out) return fail(E_ARG, "mrl_obfilter_update_apply: null out");
+  if (!(clip > 0.0)) return fail(E_ARG, "mrl_obfilter_update_apply: clip must be positive");
+  if (!workspace) return fail(E_ARG, "mrl_obfilter_update_apply: null workspace (mrl_obfilter_workspace_bytes)");
+  const int64_t nb = (n_rows + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK;
+  const unsigned chunks = (unsigned)((dim + LCOLS - 1) / LCOLS);
+  double* ws = reinterpret_cast<double*>(workspace);
+  double* stage = ws + nb * (2 + 2 * ((int64_t)dim + 1));
+  hipStream_t s = (hipStream_t)stream;
+  if (update)
+    hipLaunchKernelGGL(obfilter_partials_kernel, dim3((unsigned)nb, chunks), dim3(RB), 0, s, x, n_rows, dim, ws);
+  hipLaunchKernelGGL(obfilter_merge_kernel, dim3(chunks), dim3(LCOLS), 0, s, state, dim, (int)nb, update != 0, ws);
+  hipLaunchKernelGGL(obfilter_apply_kernel, dim3((unsigned)nb, chunks), dim3(RB), 0, s, x, n_rows, dim, clip, stage,
+                     out, update ? state : nullptr);
+  return hip_check(hipGetLastError(), "mrl_obfilter_update_apply");
 }
 
 }  // extern "C"

@@ -1,9 +1,10 @@
 """Env registry for the device env steppers (replaces ``gym.envs.make``, run_pg.py:85).
 
-The dynamics live in ``csrc/envs.h`` and run inside the fused rollout kernel; this
-module only describes them with gym-compatible spaces / spec so that
+The dynamics live in ``csrc/envs.h`` / ``csrc/humanoid.h`` and run inside the rollout
+kernels; this module describes them with gym-compatible spaces / spec so that
 ``TrpoAgent(env.observation_space, env.action_space, cfg)`` and
-``env.spec.max_episode_steps`` (run_pg.py:103-108) work unchanged.
+``env.spec.max_episode_steps`` (run_pg.py:103-108) work unchanged, and ``VecEnv`` steps
+them with the caller's own actions (``mrl_env_reset`` / ``mrl_env_step``).
 
 * ``CartPole-v0`` -- gym's classic-control CartPole equations, TimeLimit 200.
 * ``Hopper-v2``   -- gym's hopper.xml as articulated rigid-body dynamics (obs 11, act 3, TimeLimit 1000);
@@ -11,7 +12,10 @@ module only describes them with gym-compatible spaces / spec so that
 * ``Humanoid-v2`` -- Humanoid-v2-SHAPED surrogate (obs 376, act 17 in [-0.4, 0.4],
   TimeLimit 1000); its 376-d obs needs the layered rollout (collector.py).
 """
+import ctypes
+
 import numpy as np
+import torch
 
 from . import _lib
 
@@ -50,7 +54,14 @@ REGISTRY = {
 
 
 class DeviceEnv:
-    """Description of a batched device env (the state itself lives in a Collector)."""
+    """Description of a batched device env (a Collector or a ``VecEnv`` holds the state).
+
+    ``reset()`` / ``step(a)`` make it a gym-shaped single env, so the reference's serial
+    ``rollout(env, agent, limit)`` loop (core.py:186-204) runs as written: they drive a
+    lazily created one-env ``VecEnv`` without auto-reset and return numpy values.  Every
+    step is one kernel launch and one device-to-host copy -- a convenience for evaluation
+    and debugging; ``vec(n_envs)`` is the batched interface.
+    """
 
     def __init__(self, env_id):
         if env_id not in REGISTRY:
@@ -64,9 +75,116 @@ class DeviceEnv:
         self.discrete = r["discrete"]
         self.act_dim = r["act"]
         self.spec = EnvSpec(env_id, r["max_steps"])
+        self._seed = 0
+        self._single = None
 
     def close(self):
-        pass
+        self._single = None
+
+    def vec(self, n_envs, **kw):
+        """A ``VecEnv`` of ``n_envs`` copies of this env."""
+        return VecEnv(self, n_envs, **kw)
+
+    def seed(self, seed=0):
+        """Seed of the reset-noise stream of ``reset()`` / ``step()`` (restarts the env)."""
+        self._seed = int(seed)
+        self._single = None
+        return [self._seed]
+
+    def reset(self):
+        if self._single is None:
+            self._single = VecEnv(self, 1, seed=self._seed, auto_reset=False)
+        return self._single.reset()[0].cpu().numpy()
+
+    def step(self, action):
+        if self._single is None:
+            raise RuntimeError("step() before reset()")
+        a = np.asarray(action)
+        ob, rew, done, _ = self._single.step(a.reshape((1,) if self.discrete else (1, self.act_dim)))
+        return ob[0].cpu().numpy(), float(rew[0]), bool(done[0]), {}
+
+
+class VecEnv:
+    """``n_envs`` device envs stepped in lock-step with the caller's actions (gym's
+    vector-env shape), on the same HIP dynamics and reset streams as the rollout.
+
+    ``reset(mask=None)`` returns ``obs``, the raw float64 ``[E, obs_dim]`` observations;
+    ``step(actions)`` returns ``(obs, rew, done, info)`` with ``done = flags & 1`` and
+    ``info = {"flags", "terminated", "ep_t", "final_obs"}`` (flags bit 0: episode ended,
+    bit 1: terminated by the env or its TimeLimit; ``ep_t``: the step's index in its
+    episode).  With ``auto_reset`` an ended env is reset inside the same call: its ``obs``
+    row is the new episode's first observation and ``info["final_obs"]`` holds the
+    observation that ended the old one (rows of other envs there are stale).  Without it
+    nothing resets; stepping an ended env goes on integrating, as in gym.
+
+    The returned tensors belong to the env and are overwritten by the next call; clone
+    what must be kept.  ``timestep_limit=None`` is the env's own ``max_episode_steps``.
+    """
+
+    def __init__(self, env_id, n_envs, seed=0, timestep_limit=None, auto_reset=True, env_offset=0, device="cuda"):
+        env = env_id if isinstance(env_id, DeviceEnv) else DeviceEnv(env_id)
+        if int(n_envs) <= 0:
+            raise ValueError(f"n_envs must be positive, got {n_envs}")
+        lib = _lib.load(require_gpu=True)
+        self.env, self.E = env, int(n_envs)
+        self.observation_space, self.action_space, self.spec = env.observation_space, env.action_space, env.spec
+        self.auto_reset = bool(auto_reset)
+        self.dev = torch.device(device)
+        limit = env.spec.max_episode_steps if timestep_limit is None else int(timestep_limit)
+        self.desc = _lib.RolloutDesc(env.kind, self.E, 1, limit, 0, int(env_offset), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                     _lib.COMPUTE_F32, 0)
+        E, O, A = self.E, env.obs_dim, env.act_dim
+        f64 = dict(dtype=torch.float64, device=self.dev)
+        self.env_state = torch.zeros(int(lib.mrl_env_state_doubles(env.kind)) * E, **f64)
+        self.env_int = torch.zeros(2 * E, dtype=torch.int32, device=self.dev)
+        self.obs = torch.zeros(E, O, **f64)
+        self.final_obs = torch.zeros(E, O, **f64)
+        self.rew = torch.zeros(E, **f64)
+        self.flags = torch.zeros(E, dtype=torch.uint8, device=self.dev)
+        self.ep_t = torch.zeros(E, dtype=torch.int32, device=self.dev)
+        self._act = (torch.zeros(E, dtype=torch.int32, device=self.dev) if env.discrete
+                     else torch.zeros(E, A, dtype=torch.float32, device=self.dev))
+        self._mask = torch.zeros(E, dtype=torch.uint8, device=self.dev)
+        self._bufs = _lib.RolloutBufs(env_state=_lib.ptr(self.env_state), env_int=_lib.ptr(self.env_int))
+
+    @property
+    def episodes_started(self):
+        """int32 [E]: resets of every env so far (the reset-noise stream's counter)."""
+        return self.env_int[self.E:]
+
+    def _io(self, mask=None):
+        p = _lib.ptr
+        return _lib.EnvIO(p(self._act), p(mask), p(self.obs), p(self.rew), p(self.flags), p(self.ep_t),
+                          p(self.final_obs))
+
+    def reset(self, mask=None):
+        """Reset every env, or those where ``mask`` ([E], non-zero / True) is set."""
+        m = None
+        if mask is not None:
+            mk = torch.as_tensor(mask)
+            if tuple(mk.shape) != (self.E,):
+                raise ValueError(f"mask must have shape ({self.E},), got {tuple(mk.shape)}")
+            self._mask.copy_(mk != 0)
+            m = self._mask
+        _lib.call("mrl_env_reset", ctypes.byref(self.desc), ctypes.byref(self._bufs), ctypes.byref(self._io(m)),
+                  _lib.stream())
+        return self.obs
+
+    def step(self, actions):
+        a = torch.as_tensor(actions)
+        want = tuple(self._act.shape)
+        if tuple(a.shape) != want:
+            raise ValueError(f"actions must have shape {want}, got {tuple(a.shape)}")
+        integral = not (a.dtype.is_floating_point or a.dtype.is_complex or a.dtype == torch.bool)
+        if self.env.discrete and not integral:
+            raise ValueError(f"a discrete env takes integer action indices, got {a.dtype}")
+        if not self.env.discrete and not a.dtype.is_floating_point:
+            raise ValueError(f"a continuous env takes floating-point actions, got {a.dtype}")
+        self._act.copy_(a)
+        _lib.call("mrl_env_step", ctypes.byref(self.desc), ctypes.byref(self._bufs), ctypes.byref(self._io()),
+                  int(self.auto_reset), _lib.stream())
+        info = dict(flags=self.flags, terminated=(self.flags & 2) != 0, ep_t=self.ep_t, final_obs=self.final_obs)
+        return self.obs, self.rew, (self.flags & 1) != 0, info
 
 
 def make(env_id):
