@@ -17,6 +17,7 @@
  */
 #ifndef MRL_HIP_H
 #define MRL_HIP_H
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -558,6 +559,51 @@ int mrl_env_step(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, const mrl
 int64_t mrl_obfilter_workspace_bytes(int64_t n_rows, int32_t dim);
 int mrl_obfilter_update_apply(double* state, int32_t dim, const double* x, int64_t n_rows, int32_t update,
                               double clip, float* out, void* workspace, void* stream);
+
+/* ---------------------------------------------------------------- cross-entropy method
+ * The reference's second algorithm (cem.py:10-50, run_cem.py): each generation scores a
+ * population of N parameter vectors with one whole episode per vector (cem.py:64-68,
+ * `rollout(env, agent, limit)["reward"].sum()` under DeterministicAgent, agentzoo.py:116-123).
+ * mrl_pop_rollout runs the N episodes in one launch: env e is driven by parameter vector e. */
+typedef struct {
+  double*  ret;        /* [N] undiscounted sum of raw rewards, added in step order in fp64 */
+  int32_t* len;        /* [N] steps taken */
+  uint8_t* flags;      /* [N] bit 1 = terminated (env done or the env's own TimeLimit), as mrl_env_step;
+                          bit 0 (episode ended) is always set */
+  double*  stat;       /* [N, 1 + 2*obs_dim]: count, mean[obs_dim], M2[obs_dim] (Welford, fp64) of the raw
+                          observations the policy was fed (steps 0 .. len-1, not the final one) */
+  /* optional trace, all NULL or all set; rows beyond len[i] are left untouched */
+  int32_t  trace_steps;
+  double*  trace_obs;  /* [trace_steps, N, obs_dim] raw */
+  void*    trace_act;  /* [trace_steps, N, act_dim] f32, or [trace_steps, N] int32 */
+  double*  trace_rew;  /* [trace_steps, N] */
+} mrl_pop_io;
+
+/* Every env e < d->n_envs starts a new episode (the reset stream and counter update of
+ * mrl_env_reset) and runs it to its end under the deterministic policy of thetas + e*ld_theta
+ * (flat fp32 theta, Keras order; the Gauss head's mean | argmax of the logits, ties to the
+ * lowest index): done, the env's TimeLimit, or d->timestep_limit when > 0.  ld_theta == 0: one
+ * theta for every env (evaluation of a trained policy over N episodes).  filter_state: a
+ * ZFilter state (mrl_filter_doubles layout), frozen for the call -- the policy sees what
+ * mrl_obfilter_update_apply(update = 0, clip = 5) gives; NULL or n_obs < 2: the raw
+ * observation, clipped only.  From the desc: env_id, n_envs, timestep_limit, env_offset, seed;
+ * from the bufs: env_state, env_int.  CartPole / Hopper with their 64-64 policy nets; anything
+ * else is MRL_E_UNSUPPORTED. */
+int mrl_pop_rollout(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, const mrl_mlp_desc* pol,
+                    const float* thetas, int64_t ld_theta, const double* filter_state,
+                    const mrl_pop_io* io, void* stream);
+
+/* thetas[i, p] = (float)(mean[p] + sample_std[p] * z(i, p)), product and sum in fp64 (cem.py:42);
+ * z: Box-Muller (as the rollout's sampling noise) of Philox (seed, domain 2, gid i, word
+ * generation, call p / 2) */
+int mrl_cem_sample(const double* mean, const double* sample_std, int64_t P, int64_t N, uint64_t seed,
+                   uint64_t generation, float* thetas, int64_t ld_theta, void* stream);
+/* elite refit (cem.py:46-49): the n_elite largest ys under the total order (y, index) -- a NaN
+ * is lowest, ties go to the higher index -- listed ascending in elite_idx; mean_out [P] their
+ * fp64 mean, var_out [P] their population variance (ddof 0, two passes, fp64) */
+size_t mrl_cem_refit_workspace_bytes(int64_t N, int64_t P);
+int mrl_cem_refit(const float* thetas, int64_t ld_theta, int64_t N, int64_t P, const double* ys,
+                  int32_t n_elite, double* mean_out, double* var_out, int32_t* elite_idx, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------- streams
  * CU-masked HIP streams for the iteration pipeline (the rollout of iteration k+1

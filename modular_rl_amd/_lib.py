@@ -78,6 +78,11 @@ class EnvIO(ctypes.Structure):
     _fields_ = [("act", vp), ("mask", vp), ("obs", vp), ("rew", vp), ("flags", vp), ("ep_t", vp), ("final_obs", vp)]
 
 
+class PopIO(ctypes.Structure):
+    _fields_ = [("ret", vp), ("len", vp), ("flags", vp), ("stat", vp), ("trace_steps", i32), ("trace_obs", vp),
+                ("trace_act", vp), ("trace_rew", vp)]
+
+
 # name -> (restype, argtypes); every symbol include/mrl_hip.h declares
 SIGNATURES = {
     "mrl_last_error": (ctypes.c_char_p, []),
@@ -170,6 +175,10 @@ SIGNATURES = {
     "mrl_env_step": (i32, [vp, vp, vp, i32, vp]),
     "mrl_obfilter_workspace_bytes": (i64, [i64, i32]),
     "mrl_obfilter_update_apply": (i32, [vp, i32, vp, i64, i32, f64, vp, vp, vp]),
+    "mrl_pop_rollout": (i32, [vp, vp, vp, vp, i64, vp, vp, vp]),
+    "mrl_cem_sample": (i32, [vp, vp, i64, i64, ctypes.c_uint64, ctypes.c_uint64, vp, i64, vp]),
+    "mrl_cem_refit_workspace_bytes": (ctypes.c_size_t, [i64, i64]),
+    "mrl_cem_refit": (i32, [vp, i64, i64, i64, vp, i32, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -149,3 +149,58 @@ class PpoSgdAgent(TrpoAgent):
     """`agentzoo.py:143-150`: PPO with minibatch Adam."""
     options = MLP_OPTIONS + PG_OPTIONS + PpoSgdUpdater.options + FILTER_OPTIONS
     updater_cls = PpoSgdUpdater
+
+
+class FrozenZFilter:
+    """The observation filter of a ``DeterministicAgent`` for single observations
+    (``agent.obfilt(ob)``): what ``mrl_pop_rollout`` feeds its policies -- the agent's
+    ``filter_state`` applied without updating it, clip 5; with fewer than two observations
+    in the state the observation is only clipped.  ``run_cem_algorithm`` is what updates
+    the state, between generations."""
+
+    def __init__(self, agent, clip=5.0):
+        self.agent, self.clip = agent, clip
+
+    def __call__(self, x, update=False):
+        x = np.asarray(x, dtype=np.float64)
+        fs = self.agent.filter_state.cpu().numpy()
+        O = x.shape[-1]
+        D = (fs.size - 2) // 2
+        if fs[0] >= 2:
+            x = (x - fs[2:2 + O]) / (np.sqrt(fs[2 + D:2 + D + O] / (fs[0] - 1)) + 1e-8)
+        return np.clip(x, -self.clip, self.clip)
+
+
+class DeterministicAgent(AgentWithPolicy):
+    """`agentzoo.py:116-123`: an MLP policy acting deterministically (the Gauss mean / the
+    most probable action), with no baseline and no updater, trained derivative-free by
+    ``run_cem_algorithm``.  ``filter_state`` is the ZFilter state (``mrl_filter_doubles``
+    layout, float64 on the device) that the population rollout reads and
+    ``run_cem_algorithm`` updates between generations; ``None`` with ``filter=0``.
+    ``act`` / ``obfilt`` serve the reference's serial ``rollout(env, agent, limit)`` with
+    the same frozen filter; ``rewfilt`` is the identity (CEM uses raw returns)."""
+    options = MLP_OPTIONS + FILTER_OPTIONS
+
+    def __init__(self, ob_space, ac_space, usercfg):
+        import torch
+        cfg = update_default_config(self.options, usercfg)
+        self.cfg = cfg
+        assert isinstance(ob_space, Box)
+        if cfg["activation"] != "tanh":
+            raise _lib.MrlError("only activation=tanh is implemented on the HIP path")
+        hid = check_hid_sizes(cfg["hid_sizes"])
+        seed = int((usercfg or {}).get("seed", 0) or 0)
+        if isinstance(ac_space, Box):
+            outdim, head, probtype = ac_space.shape[0], _lib.HEAD_GAUSS, DiagGauss(ac_space.shape[0])
+        else:
+            outdim, head, probtype = ac_space.n, _lib.HEAD_SOFTMAX, Categorical(ac_space.n)
+        nin = ob_space.shape[0]
+        net = make_net(nin, outdim, head, hid, impl=cfg.get("mlp_impl", "auto"), dtype=cfg.get("mlp_dtype", "fp32"))
+        net.set_flat(glorot_init(np.random.default_rng(seed), nin, outdim, head, hid))
+        self.filter_state = None
+        obfilter = IDENTITY
+        if cfg["filter"]:
+            self.filter_state = torch.zeros(2 + 2 * (nin + 1), dtype=torch.float64, device=net.theta.device)
+            obfilter = FrozenZFilter(self)
+        AgentWithPolicy.__init__(self, StochPolicyMLP(net, probtype), obfilter, IDENTITY)
+        self.set_stochastic(False)

@@ -66,8 +66,15 @@ def capture_state(agent, with_vf=True, host=True, theta=True):
     rest, capture_host_state, after it); theta=False: without the policy parameters
     (the runner clones them after issuing that rollout, which only reads them)."""
     cap = {"policy/theta": agent.policy.net.theta.detach().clone()} if theta else {}
-    if with_vf:
+    if with_vf and getattr(agent, "baseline", None) is not None:
         cap["vf/theta"] = agent.baseline.net.theta.detach().clone()
+    if not hasattr(agent, "_filter_owner"):
+        # a DeterministicAgent: no baseline, no collector; it holds its ZFilter state itself
+        if getattr(agent, "filter_state", None) is not None:
+            cap["filter/state"] = agent.filter_state.detach().clone()
+        if host:
+            cap.update(capture_host_state(agent))
+        return cap
     col = agent._filter_owner()
     if col is not None:
         cap["filter/state"] = col.filter_state[:col.FS].detach().clone()
@@ -129,8 +136,20 @@ def load_snapshot(path, agent):
                              f"which this agent's {type(upd).__name__} needs to resume exactly")
     elif version != SNAPSHOT_VERSION:
         raise ValueError(f"{path}: snapshot version {version} != {SNAPSHOT_VERSION}")
-    pol, vf = agent.policy.net, agent.baseline.net
-    if st["policy/theta"].shape != (pol.P,) or st["vf/theta"].shape != (vf.P,):
+    pol = agent.policy.net
+    if getattr(agent, "baseline", None) is None:
+        # a DeterministicAgent: the policy and its own ZFilter state are all there is
+        if st["policy/theta"].shape != (pol.P,):
+            raise ValueError(f"{path}: parameter shapes do not match this agent's net")
+        has_fs, wants_fs = "filter/state" in st, getattr(agent, "filter_state", None) is not None
+        if has_fs != wants_fs or (has_fs and st["filter/state"].shape != tuple(agent.filter_state.shape)):
+            raise ValueError(f"{path}: snapshot filter state does not match this agent's filter setting")
+        pol.set_flat(st["policy/theta"])
+        if has_fs:
+            agent.filter_state.copy_(torch.as_tensor(st["filter/state"], dtype=torch.float64))
+        return meta
+    vf = agent.baseline.net
+    if st["policy/theta"].shape != (pol.P,) or st.get("vf/theta", np.empty(0)).shape != (vf.P,):
         raise ValueError(f"{path}: parameter shapes do not match this agent's nets")
     pol.set_flat(st["policy/theta"])
     vf.set_flat(st["vf/theta"])

@@ -189,3 +189,93 @@ class VecEnv:
 
 def make(env_id):
     return DeviceEnv(env_id)
+
+
+class PopulationRollout:
+    """``n`` whole episodes in one launch, env ``i`` driven by parameter vector ``i``
+    (``mrl_pop_rollout``): the objective of the cross-entropy method (cem.py:64-68, one
+    ``rollout(env, agent, limit)["reward"].sum()`` per candidate) under the deterministic
+    policy (the Gauss head's mean / the arg-max logit).
+
+    ``pop(thetas, filter_state=None, trace_steps=0)`` takes float32 ``[n, P]`` device rows
+    (flat Keras-order theta of the env's 64-64 policy net) and returns a dict of tensors the
+    object owns: ``ret`` (float64 sum of raw rewards), ``len``, ``flags`` (bit 1:
+    terminated), ``stat`` (``[n, 1 + 2 obs_dim]`` Welford count / mean / M2 of the raw
+    observations each policy was fed) and, with ``trace_steps > 0``, ``trace_obs`` /
+    ``trace_act`` / ``trace_rew`` (rows beyond ``len[i]`` are left as they were).
+    ``filter_state`` is a ``BatchZFilter.state`` / Collector ``filter_state[:FS]``, frozen for
+    the call; ``None`` (or fewer than two observations in it) feeds the raw observation,
+    clipped to +-5.  ``evaluate(theta, ...)`` runs one theta in all ``n`` envs.
+
+    Every call starts a new episode in every env: the reset stream is the ``VecEnv``'s
+    (seed, env, episodes started), so a ``VecEnv`` with the same seed replays a traced call.
+    """
+
+    def __init__(self, env_id, n, seed=0, timestep_limit=None, env_offset=0, device="cuda"):
+        env = env_id if isinstance(env_id, DeviceEnv) else DeviceEnv(env_id)
+        if int(n) <= 0:
+            raise ValueError(f"n must be positive, got {n}")
+        lib = _lib.load(require_gpu=True)
+        self.env, self.N = env, int(n)
+        self.dev = torch.device(device)
+        limit = env.spec.max_episode_steps if not timestep_limit else int(timestep_limit)
+        self.limit = min(limit, env.spec.max_episode_steps)
+        self.desc = _lib.RolloutDesc(env.kind, self.N, 1, self.limit, 0, int(env_offset),
+                                     int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.COMPUTE_F32, 0)
+        head = _lib.HEAD_SOFTMAX if env.discrete else _lib.HEAD_GAUSS
+        self.pol = _lib.MlpDesc(env.obs_dim, env.act_dim, head, 64, 2)
+        self.P = int(lib.mrl_mlp_num_params(ctypes.byref(self.pol)))
+        N, O = self.N, env.obs_dim
+        f64 = dict(dtype=torch.float64, device=self.dev)
+        self.env_state = torch.zeros(int(lib.mrl_env_state_doubles(env.kind)) * N, **f64)
+        self.env_int = torch.zeros(2 * N, dtype=torch.int32, device=self.dev)
+        self.ret = torch.zeros(N, **f64)
+        self.len = torch.zeros(N, dtype=torch.int32, device=self.dev)
+        self.flags = torch.zeros(N, dtype=torch.uint8, device=self.dev)
+        self.stat = torch.zeros(N, 1 + 2 * O, **f64)
+        self._trace = None
+        self._bufs = _lib.RolloutBufs(env_state=_lib.ptr(self.env_state), env_int=_lib.ptr(self.env_int))
+
+    @property
+    def episodes_started(self):
+        """int32 [n]: episodes every env has started (the reset-noise stream's counter)."""
+        return self.env_int[self.N:]
+
+    def _trace_bufs(self, steps):
+        if self._trace is None or self._trace[0].shape[0] < steps:
+            N, O, A = self.N, self.env.obs_dim, self.env.act_dim
+            act = (torch.zeros(steps, N, dtype=torch.int32, device=self.dev) if self.env.discrete
+                   else torch.zeros(steps, N, A, dtype=torch.float32, device=self.dev))
+            self._trace = (torch.zeros(steps, N, O, dtype=torch.float64, device=self.dev), act,
+                           torch.zeros(steps, N, dtype=torch.float64, device=self.dev))
+        return tuple(t[:steps] for t in self._trace)
+
+    def _run(self, thetas, ld, filter_state, trace_steps):
+        p = _lib.ptr
+        fs = None
+        if filter_state is not None:
+            fs = torch.as_tensor(filter_state, dtype=torch.float64).to(self.dev).contiguous()
+            if fs.numel() < 2 + 2 * (self.env.obs_dim + 1):
+                raise ValueError("filter_state must hold n_obs, n_rew, M[obs_dim + 1], S[obs_dim + 1]")
+        out = dict(ret=self.ret, len=self.len, flags=self.flags, stat=self.stat)
+        io = _lib.PopIO(p(self.ret), p(self.len), p(self.flags), p(self.stat))
+        if int(trace_steps) > 0:
+            tobs, tact, trew = self._trace_bufs(int(trace_steps))
+            io.trace_steps, io.trace_obs, io.trace_act, io.trace_rew = int(trace_steps), p(tobs), p(tact), p(trew)
+            out.update(trace_obs=tobs, trace_act=tact, trace_rew=trew)
+        _lib.call("mrl_pop_rollout", ctypes.byref(self.desc), ctypes.byref(self._bufs), ctypes.byref(self.pol),
+                  p(thetas), ld, p(fs), ctypes.byref(io), _lib.stream())
+        return out
+
+    def _theta(self, th, shape):
+        th = torch.as_tensor(th)
+        if tuple(th.shape) != shape:
+            raise ValueError(f"expected parameters of shape {shape}, got {tuple(th.shape)}")
+        return th.to(device=self.dev, dtype=torch.float32).contiguous()
+
+    def __call__(self, thetas, filter_state=None, trace_steps=0):
+        return self._run(self._theta(thetas, (self.N, self.P)), self.P, filter_state, trace_steps)
+
+    def evaluate(self, theta, filter_state=None, trace_steps=0):
+        """The same ``theta`` in all ``n`` envs: a trained policy's return over ``n`` episodes."""
+        return self._run(self._theta(theta, (self.P,)), 0, filter_state, trace_steps)
