@@ -1,7 +1,9 @@
 // Cross-entropy method, the two steps around the population rollout (cem.py:32-50):
 //   mrl_cem_sample  ths = th_mean + sample_std * randn(batch_size, P)          cem.py:42
 //   mrl_cem_refit   elite_inds = ys.argsort()[-n_elite:]; mean / var of them  cem.py:46-49
-// The population stays on the device between them (mrl_pop_rollout reads it in place).
+// The population stays on the device between them (mrl_pop_rollout, pop_rollout.hip, reads it in
+// place; that unit includes the env headers, which set the fp contraction of what follows them,
+// so these kernels stay in a unit without them).
 #include <math.h>
 
 #include "../../include/mrl_hip.h"

@@ -61,7 +61,7 @@ __device__ inline void cartpole_obs(const double* s, double* o) {
 // (M_tt = total mass * I) eliminated by its Schur complement; a 4x4 LDL^T solve;
 // semi-implicit Euler.  frame_skip 4 x dt 0.002.  The fused step kernel splits
 // the contact work and the angle functions over the four 16-lane rows that hold
-// the same envs (HopperQuad, rollout.hip); everything else is evaluated by every
+// the same envs (HopperQuad, rollout_device.h); everything else is evaluated by every
 // row in the same order, so all rows continue with the identical state.
 constexpr int HP_NS = 12, HP_OBS = 11, HP_ACT = 3;
 constexpr double HP_DT = 0.002;

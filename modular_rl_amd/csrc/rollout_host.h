@@ -1,0 +1,128 @@
+// Host-side glue shared by the rollout units -- rollout.hip, rollout_layered.hip, env_api.hip
+// and the population rollout in cem.hip: the descriptor checks, the launch arguments, the
+// dispatch of an env id or a flag onto a kernel template, and the launch of the Humanoid
+// wave-per-env kernels.  The error state (fail / hip_check, mrl_common.h) is mlp_kernels.hip's.
+#pragma once
+#include <stdlib.h>
+
+#include <type_traits>
+
+#include "rollout_device.h"
+
+namespace mrl {
+
+inline int check_roll(const mrl_rollout_desc* d, const mrl_rollout_bufs* b) {
+  if (!d || !b) return fail(E_ARG, "null desc/bufs");
+  if (d->env_id != MRL_ENV_CARTPOLE && d->env_id != MRL_ENV_HOPPER && d->env_id != MRL_ENV_HUMANOID)
+    return fail(E_UNSUPPORTED, "unknown env_id");
+  if (d->n_envs <= 0 || d->horizon <= 0 || d->timestep_limit <= 0) return fail(E_ARG, "bad sizes");
+  if (d->compute != MRL_COMPUTE_F32 && d->compute != MRL_COMPUTE_BF16) return fail(E_ARG, "bad compute");
+  if (!b->env_state || !b->env_int || !b->filter_state || !b->records || !b->iteration) return fail(E_ARG, "null state");
+  return OK;
+}
+
+// blocks of ENVS_PER_BLOCK envs (or filter rows) covering n
+inline int64_t env_blocks(int64_t n) { return (n + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK; }
+
+inline RollArgs make_args(const mrl_rollout_desc* d, const mrl_rollout_bufs* b) {
+  RollArgs a;
+  a.d = *d;
+  a.b = *b;
+  a.nb = (int)env_blocks(d->n_envs);
+  a.FS = filt_doubles(env_info(d->env_id).obs);
+  a.RS = a.FS;
+  return a;
+}
+
+inline int check_fused_policy(const mrl_rollout_desc* d, const mrl_mlp_desc* pol) {
+  EnvInfo ei = env_info(d->env_id);
+  const bool gauss = pol->head == MRL_HEAD_GAUSS;
+  if (pol->n_in != ei.obs || pol->n_out != ei.act || gauss == (bool)ei.discrete || pol->n_hidden != HID ||
+      pol->n_layers != 2)
+    return fail(E_ARG, "policy shape does not match the env");
+  return OK;
+}
+
+// the arguments mrl_rollout_run and mrl_rollout_step share
+inline int check_fused_run(const mrl_rollout_desc* d, const mrl_mlp_desc* pol, const float* theta, const float* rimage,
+                           const mrl_rollout_bufs* b) {
+  int rc = check_roll(d, b);
+  if (rc) return rc;
+  if (!pol || !theta || !rimage) return fail(E_ARG, "null policy");
+  if (d->env_id == MRL_ENV_HUMANOID) return fail(E_UNSUPPORTED, "Humanoid runs on the layered rollout");
+  if (!b->obs || !b->act || !b->prob || !b->rew || !b->flags || !b->ep_t) return fail(E_ARG, "null trajectory buffer");
+  if (!b->noise) return fail(E_ARG, "bufs.noise: sampling-noise rows (mrl_rollout_noise or injected) required");
+  return check_fused_policy(d, pol);
+}
+
+// ------------------------------------------------------------------ dispatch
+// A kernel template <int ENV> launched for a run-time env id: all three envs ...
+#define MRL_DISPATCH_ENV(id, KERNEL, ...)                                                    \
+  do {                                                                                      \
+    if ((id) == MRL_ENV_CARTPOLE) hipLaunchKernelGGL(KERNEL<MRL_ENV_CARTPOLE>, __VA_ARGS__); \
+    else if ((id) == MRL_ENV_HOPPER) hipLaunchKernelGGL(KERNEL<MRL_ENV_HOPPER>, __VA_ARGS__); \
+    else hipLaunchKernelGGL(KERNEL<MRL_ENV_HUMANOID>, __VA_ARGS__);                         \
+  } while (0)
+
+// ... or the two that are stepped by a thread per env (CartPole, Hopper; the callers have
+// turned Humanoid away or launch its wave-per-env kernel): f(integral_constant<int, ENV>)
+template <class F>
+inline void dispatch_env2(int id, F&& f) {
+  if (id == MRL_ENV_CARTPOLE) f(std::integral_constant<int, MRL_ENV_CARTPOLE>{});
+  else f(std::integral_constant<int, MRL_ENV_HOPPER>{});
+}
+#define MRL_DISPATCH_ENV2(id, KERNEL, ...) \
+  dispatch_env2((id), [&](auto env) { hipLaunchKernelGGL(KERNEL<env()>, __VA_ARGS__); })
+
+// a run-time flag as a template argument: f(std::true_type) or f(std::false_type)
+template <class F>
+inline void dispatch_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// ------------------------------------------------------------------ Humanoid launch
+// Dynamic LDS padding for the wave-per-env Humanoid step: while the envs fit one wave
+// per SIMD, at most 4 blocks (waves) may share a CU, so the dispatcher cannot stack two
+// latency chains on one SIMD and leave another idle.
+inline size_t hm_lds_pad(int n_envs) {
+  static int ncu = 0;
+  if (ncu == 0) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
+      ncu = n;
+    else
+      ncu = -1;
+  }
+  if (ncu <= 0 || n_envs > 4 * ncu) return 0;
+  constexpr size_t LDS_CU = 160 * 1024, used = sizeof(hm::Wave) + sizeof(hm::Shared), want = LDS_CU / 5 + 1024;
+  return used < want ? want - used : 0;
+}
+// MRL_HM_WPB (per launch): four envs per block (hm_block, the default) or 1
+inline int hm_wpb() {
+  // r04i (C5 bf16, 1024 envs): the rollout alone 225 -> 212 ms per iteration, beside the
+  // co-scheduled fit 269 -> 260 ms (one table copy per four envs, 94 KB of LDS per CU)
+  const char* e = getenv("MRL_HM_WPB");
+  return (e && atoi(e) == 1) ? 1 : 4;
+}
+// dynamic LDS of a launch (the static tables / state come on top): the WPB = 4 states, and
+// for the step kernels the one-wave block's padding
+inline size_t hm_lds_state(int wpb, int) { return wpb == 1 ? 0 : (size_t)wpb * sizeof(hm::Wave); }
+inline size_t hm_lds_bytes(int wpb, int n_envs) { return wpb == 1 ? hm_lds_pad(n_envs) : hm_lds_state(wpb, n_envs); }
+
+// a kernel template <int WPB> over n_envs envs, a wave each: hm_wpb() envs per block, LDS
+// (hm_lds_state for the reset kernels, hm_lds_bytes for the step kernels) bytes of dynamic LDS
+#define MRL_LAUNCH_HM(KERNEL, LDS, n_envs, stream, ...)                                  \
+  do {                                                                                   \
+    const int wpb_ = hm_wpb();                                                           \
+    const dim3 gb_(((n_envs) + wpb_ - 1) / wpb_), bb_(64 * wpb_);                         \
+    const size_t lds_ = LDS(wpb_, (n_envs));                                             \
+    if (wpb_ == 4) hipLaunchKernelGGL(KERNEL<4>, gb_, bb_, lds_, (stream), __VA_ARGS__); \
+    else hipLaunchKernelGGL(KERNEL<1>, gb_, bb_, lds_, (stream), __VA_ARGS__);           \
+  } while (0)
+
+// hm_env_reset_kernel / hm_env_step_kernel (rollout_layered.hip) for mrl_env_reset / mrl_env_step
+void launch_hm_env_reset(const RollArgs& a, const mrl_env_io& io, hipStream_t s);
+void launch_hm_env_step(const RollArgs& a, const mrl_env_io& io, int auto_reset, hipStream_t s);
+
+}  // namespace mrl

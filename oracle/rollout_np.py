@@ -4,9 +4,10 @@ Follows the reference's per-step loop (`core.py:182-207`: obfilt -> act -> step 
 rewfilt) for E envs in lock-step, with the batched-filter rule of SURVEY Appendix
 A.1 (all E observations of a step merged into the running stat -- as per-block
 Welford partials in block order -- then normalised).  For E = 1 this is exactly
-the reference's sequence of RunningStat.push calls.  Mirrors
-``modular_rl_amd/csrc/rollout.hip`` step for step so the GPU collector can be
-checked row by row; the policy forward here is float64 on the stored float32
+the reference's sequence of RunningStat.push calls.  Mirrors the rollout units of
+``modular_rl_amd/csrc`` (``rollout.hip`` the fused path, ``rollout_layered.hip`` the
+layered one, ``rollout_device.h`` what they share) step for step so the GPU collector
+can be checked row by row; the policy forward here is float64 on the stored float32
 observations.
 """
 import numpy as np

@@ -1,6 +1,6 @@
 """Floating-point identities the kernels rely on to stay bit-identical to the oracle.
 
-* rollout.hip `div_count`: a mean over n envs divides by n; when n = 2^k the kernel
+* rollout_device.h `div_count`: a mean over n envs divides by n; when n = 2^k the kernel
   multiplies by the exact 2^-k instead.  Both are IEEE operations on the same real value
   x / 2^k, rounded once, so the results are identical -- including quotients in the
   subnormal range, signed zeros, infinities and NaN.
