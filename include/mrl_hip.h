@@ -367,7 +367,8 @@ int mrl_adam_step(float* theta, const float* g, float* m, float* v, double a_t, 
                   double eps, int64_t n, void* stream);
 /* dst row i = src row idx[i] (row_bytes a multiple of 4): PPO minibatch permutation */
 int mrl_gather_rows(const void* src, const int64_t* idx, int64_t n, int64_t row_bytes, void* dst, void* stream);
-/* out (fp64) = scale * (double)in ; in-place-safe */
+/* out (fp64) = scale * (double)in, one fp64 product per element; in and out must not
+ * overlap (out[i] covers the bytes of in[2i] and in[2i+1], which other threads still read) */
 int mrl_cast_scale_f32_f64(const float* in, double scale, int64_t n, double* out, void* stream);
 
 /* Per-row probtype values on probability rows (the reference's Categorical /
