@@ -159,18 +159,22 @@ struct JvpSplitRole {
   // the first tile's x / h1
   __device__ __forceinline__ void prologue(int64_t tile) { load_xh1(tile, xv, h1); }
   // tile `tile` (its x / h1 already loaded), prefetching tile tn's (tn == tile: re-read);
-  // PF = false: no prefetch -- the tile's own x / h1 are loaded here, after its h2 (and no
-  // prologue), so the tile's bytes all enter L2 within one round (the one-pass product's
-  // VJP role re-reads them a round later: mlp_fisher.hip)
+  // PF = false: no prefetch -- the tile's own x / h1 are loaded here (and no prologue), so
+  // the tile's bytes all enter L2 within one round (the one-pass product's VJP roles
+  // re-read them a round later: mlp_fisher.hip), and its h2 only before the h1 dW1 chain,
+  // once dh's registers are free: dh / h1 / da2, then h1 / da2 / h2 live -- three f32x16
+  // pairs, not four (166 VGPRs against 206; the other waves of the SIMD cover the load)
   template <bool PF = true, class Sink>
   __device__ __forceinline__ void tile(int64_t tile, int64_t tn, Sink&& sink) {
     const int64_t row = tile * 32 + (lane & 31);
     const bool valid = row < a.n;
     const float* ct = a.cache + tile * CACHE_TILE_FLOATS;
     f32x16 h2[2];
-    cache_load(ct, lane, 2, h2[0]);
-    cache_load(ct, lane, 3, h2[1]);
-    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (PF) {
+      cache_load(ct, lane, 2, h2[0]);
+      cache_load(ct, lane, 3, h2[1]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
     float xn[MAX_KS0B][8];
     f32x16 h1n[2];
     if constexpr (PF) load_xh1(tn, xn, h1n);
@@ -206,6 +210,11 @@ struct JvpSplitRole {
       mfma_split(img, b.fa1, PS, 1 * 4 + s, lane, ps, da2[1]);
     }
     FVP_SPLIT_FENCE();
+    if constexpr (!PF) {
+      cache_load(ct, lane, 2, h2[0]);
+      cache_load(ct, lane, 3, h2[1]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       bf16x8 ps[3];

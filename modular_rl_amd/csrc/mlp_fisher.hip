@@ -4,6 +4,8 @@
 // entry points mrl_mlp_fisher_hyb_fits, mrl_mlp_fisher_hyb, mrl_mlp_grad_hyb.
 #include <math.h>
 
+#include <type_traits>
+
 #include "fvp_split_role.h"
 #include "vjp16_device.h"
 
@@ -12,13 +14,30 @@ namespace mrl {
 // The one-pass Fisher product (mlp_fisher_hyb_kernel): the hybrid VJP above with the
 // Fisher product's JVP half beside it in the block.  Waves 0-3 (one per SIMD) run the
 // split-operand JVP rows of 32-row tiles (JvpSplitRole, fvp_split_role.h) and leave each
-// tile's KL-metric head-gradient rows in an LDS mailbox; waves 4-7 (the partner wave of
+// tile's KL-metric head-gradient rows in an LDS mailbox; waves 4-11 (two partner waves on
 // each SIMD) run this VJP on them one round later -- the tile's h1 / h2 / x re-read from
 // L2, where the JVP wave's loads of the same CU just put them, so the activation cache
 // crosses HBM once per product instead of twice, and each SIMD interleaves the JVP's VALU
 // work with the VJP's MFMA chains.  One s_barrier per round (two mailbox slots); the
 // head-gradient rows never reach HBM.
+//
+// Three waves per SIMD (168 registers each, no scratch): the VJP of a tile is divided by
+// function between the SIMD's two VJP waves, not by rows.  Role A (waves 4-7): ga2 in the
+// T layout, gW2, the b1 / b2 / logstd sums and gW1 (80 accumulator registers).  Role B
+// (waves 8-11): ga2 in the R layout, gh1, ga1 and gW0 / b0 (16).  Neither holds both
+// layouts of h2 or of ga2, each issues half of the role's MFMA chain, and every accumulator
+// sees the operations of the one-wave form in the same order (the results are bit for bit
+// those).  Both read the tile's mailbox rows and stage the tile's h1 for themselves (one
+// buffer each: all of it is in registers before the next tile's DMA is issued); the pair
+// stores disjoint parts of one slab row.
 constexpr int MBOX_GH = 2 * MAX_OUT;  // mailbox row pitch (floats): the widest head-gradient row
+// static LDS (bytes) beside the dynamic split images: the W2 fragments, one h1 staging buffer
+// per VJP wave, the split W1^T and `nslot` mailbox slots of the four producer waves
+constexpr int HYB_W2_FLOATS = 2 * 4 * 64, HYB_WBS_FRAGS = 2 * 4 * 3 * 64;
+constexpr size_t hyb_static_lds(int nslot) {
+  return (size_t)HYB_W2_FLOATS * 4 + (size_t)HYB_VJP_WAVES * VJP16_H1_FLOATS * 4 + (size_t)HYB_WBS_FRAGS * 16 +
+         (size_t)nslot * 4 * 32 * MBOX_GH * 4;
+}
 // L2 reuse of the activation cache between the roles (round 6): each role alone reads the
 // algorithmic 2.33 GB per Hopper product, the pair 4.35 GB -- the VJP role's re-reads of a
 // tile a round after the JVP role's miss the XCD's 4 MB L2 (each round brings ~4.5 MB per
@@ -47,28 +66,30 @@ struct FisherFusedIn {
 // activation cache the VJP role then reads and the surrogate head-gradient rows into the
 // mailbox, and leaves the surr / KL / entropy sums per producer wave in the partial rows
 template <int SH, int PROD = 0>
-__global__ __launch_bounds__(64 * VJP16_WAVES, 1) void mlp_fisher_hyb_kernel(VjpArgs a, const float* __restrict__ img,
-                                                                           const int32_t* __restrict__ skip,
-                                                                           FisherFusedIn fz) {
+__global__ __launch_bounds__(64 * HYB_WAVES, 1) void mlp_fisher_hyb_kernel(VjpArgs a, const float* __restrict__ img,
+                                                                         const int32_t* __restrict__ skip,
+                                                                         FisherFusedIn fz) {
   constexpr int MT0 = 1;
-  // LDS: the W2 fragments (the split W1^T of gh1 is in wbs), h1 staging of the four VJP
+  // LDS: the W2 fragments (the split W1^T of gh1 is in wbs), h1 staging of the eight VJP
   // waves, wbs, the mailbox and (dynamic) the two split images: 148 KB for Hopper
-  __shared__ __attribute__((aligned(16))) float lds[2 * 4 * 64];
-  __shared__ __attribute__((aligned(16))) float sH[4 * 2 * VJP16_H1_FLOATS];
+  // (hyb_static_lds: mrl_mlp_fisher_hyb_fits sums the same terms)
+  __shared__ __attribute__((aligned(16))) float lds[HYB_W2_FLOATS];
+  __shared__ __attribute__((aligned(16))) float sH[HYB_VJP_WAVES * VJP16_H1_FLOATS];
   // B fragments of gh1 = ga2 W1^T, [k-step s][tile nt][part p][lane], 24 KB
-  __shared__ __attribute__((aligned(16))) bf16x8 wbs[2 * 4 * 3 * 64];
+  __shared__ __attribute__((aligned(16))) bf16x8 wbs[HYB_WBS_FRAGS];
   // head-gradient rows of the JVP waves' tiles, [slot][JVP wave][row][MBOX_GH]
   // PROD 1 runs the VJP two rounds behind (LAG): its prefetch of the next tile then reads
   // cache rows the producer finished a round earlier; NSLOT mailbox slots per JVP wave
   constexpr int LAG = PROD == 1 ? 2 : 1, NSLOT = LAG + 1;
   __shared__ __attribute__((aligned(16))) float mbox[NSLOT * 4 * 32 * MBOX_GH];
+  static_assert(sizeof(lds) + sizeof(sH) + sizeof(wbs) + sizeof(mbox) == hyb_static_lds(NSLOT), "hyb_static_lds");
   extern __shared__ __attribute__((aligned(16))) float ldsx[];  // the two split images
   if (skip != nullptr && *skip != 0) return;
   const MlpDims& d = a.d;
-  for (int i = threadIdx.x; i < 2 * 4 * 64 / 4; i += 64 * VJP16_WAVES)  // BA2 of the image
+  for (int i = threadIdx.x; i < HYB_W2_FLOATS / 4; i += 64 * HYB_WAVES)  // BA2 of the image
     reinterpret_cast<float4*>(lds)[i] = reinterpret_cast<const float4*>(img + d.ba1 + 2 * 32 * 64)[i];
   const int WS = split_fwd_words(fz.rb);
-  for (int i = threadIdx.x; i < WS / 4; i += 64 * VJP16_WAVES) {
+  for (int i = threadIdx.x; i < WS / 4; i += 64 * HYB_WAVES) {
     reinterpret_cast<float4*>(ldsx)[i] = reinterpret_cast<const float4*>(fz.img_s)[i];
     if constexpr (PROD == 0) reinterpret_cast<float4*>(ldsx + WS)[i] = reinterpret_cast<const float4*>(fz.imt_s)[i];
   }
@@ -93,21 +114,24 @@ __global__ __launch_bounds__(64 * VJP16_WAVES, 1) void mlp_fisher_hyb_kernel(Vjp
   const int offT = ((c >> 3) * 64 + 32 * ((c >> 2) & 1) + 4 * g) * 4 + (c & 3);
   const int offR = ((g >> 1) * 64 + 32 * (g & 1) + c) * 4;
   {
-    // wave w builds (k-step s = w >> 2, tile nt = w & 3): lane (c, g) element e is
+    // wave w < 8 builds (k-step s = w >> 2, tile nt = w & 3): lane (c, g) element e is
     // W1[16 nt + c][16 (2 s + (e >> 2)) + 4 g + (e & 3)], i.e. w1frag(nt, 2 s + (e >> 2))
-    static_assert(VJP16_WAVES == 8, "one (s, nt) per wave");
-    const int s = wave >> 2, nt = wave & 3;
-    const float4 u = w1frag(nt, 2 * s), v = w1frag(nt, 2 * s + 1);
-    bf16x4 pu[3], pv[3];
-    split4(f32x4{u.x, u.y, u.z, u.w}, pu);
-    split4(f32x4{v.x, v.y, v.z, v.w}, pv);
+    static_assert(HYB_WAVES >= 8, "one (s, nt) per wave of the first eight");
+    if (wave < 8) {
+      const int s = wave >> 2, nt = wave & 3;
+      const float4 u = w1frag(nt, 2 * s), v = w1frag(nt, 2 * s + 1);
+      bf16x4 pu[3], pv[3];
+      split4(f32x4{u.x, u.y, u.z, u.w}, pu);
+      split4(f32x4{v.x, v.y, v.z, v.w}, pv);
 #pragma unroll
-    for (int p = 0; p < 3; ++p) wbs[((s * 4 + nt) * 3 + p) * 64 + lane] = cat4(pu[p], pv[p]);
+      for (int p = 0; p < 3; ++p) wbs[((s * 4 + nt) * 3 + p) * 64 + lane] = cat4(pu[p], pv[p]);
+    }
     __syncthreads();
   }
   // Rounds: in round r the JVP waves fill mailbox slot r & 1 with the rows of their
   // round-r tiles (32-row tile T = (r G + block) 4 + w) and the VJP waves consume slot
-  // (r - 1) & 1; every wave passes the same number of barriers (one per round)
+  // (r - 1) & 1 (both VJP roles read it); every wave passes the same number of barriers
+  // (one per round)
   const int64_t nt32 = (a.n + 31) / 32, stride32 = (int64_t)gridDim.x * 4;
   const int64_t rounds = (nt32 + stride32 - 1) / stride32 + LAG;
   auto fused_barrier = []() {
@@ -205,6 +229,10 @@ __global__ __launch_bounds__(64 * VJP16_WAVES, 1) void mlp_fisher_hyb_kernel(Vjp
     }
   }
 
+  // The VJP of the tiles, instantiated once per role (RA: the T-layout half, RB: the
+  // R-layout half; header).  Everything one role does not use is compiled out of it.
+  auto vjp_role = [&](auto role_b) {
+  constexpr bool RB = decltype(role_b)::value, RA = !RB;
   f32x4 gW1[4][4], gW2[4], gW0[MT0][4];
   f32x4 zero4 = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -227,19 +255,23 @@ __global__ __launch_bounds__(64 * VJP16_WAVES, 1) void mlp_fisher_hyb_kernel(Vjp
   // sink the load into a branch and drain every outstanding load at the join.
   float gq[2], GB[4], xA[MT0][4], xN[MT0][4];  // xN: the next tile's x, moved to xA after gW0
   f32x4 h2R[4], h2T[4], h1T[4];
-  // h2 in R and T layouts
+  // h2 in the role's layout (RB: R, RA: T)
   auto load_h2 = [&](int64_t t) {
     const float* ct = a.cache + (t >> 1) * CACHE_TILE_FLOATS + 16 * (int)(t & 1) * 4;
+    if constexpr (RB) {
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-      h2R[nt] = ldv4(reinterpret_cast<const f32x4*>(ct + (2 + (nt >> 1)) * 1024 + 512 * (nt & 1) + offR));
+      for (int nt = 0; nt < 4; ++nt)
+        h2R[nt] = ldv4(reinterpret_cast<const f32x4*>(ct + (2 + (nt >> 1)) * 1024 + 512 * (nt & 1) + offR));
+    } else {
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
+      for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) h2T[nt][r] = ldv1(ct + (2 + (nt >> 1)) * 1024 + 512 * (nt & 1) + 4 * r + offT);
+        for (int r = 0; r < 4; ++r) h2T[nt][r] = ldv1(ct + (2 + (nt >> 1)) * 1024 + 512 * (nt & 1) + 4 * r + offT);
+    }
   };
   // G of 16-row tile t from its 32-row tile's mailbox rows mbt: G[row0 + c][4 ks + g]
-  // (operand of both gh2 products), G[row0 + 4 g + r][c] (B operand of gW2, bias / logstd sums)
+  // (operand of both gh2 products), G[row0 + 4 g + r][c] (RA: B operand of gW2, bias /
+  // logstd sums)
   const float* mbt = mbox;
   auto load_g_mbox = [&](int64_t t) {
     const float* m = mbt + 16 * (int)(t & 1) * MBOX_GH;
@@ -248,19 +280,24 @@ __global__ __launch_bounds__(64 * VJP16_WAVES, 1) void mlp_fisher_hyb_kernel(Vjp
       const int o = 4 * ks + g;
       gq[ks] = m[c * MBOX_GH + (o < gh ? o : gh - 1)];
     }
+    if constexpr (RA) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) GB[r] = m[(4 * g + r) * MBOX_GH + (c < gh ? c : gh - 1)];
+      for (int r = 0; r < 4; ++r) GB[r] = m[(4 * g + r) * MBOX_GH + (c < gh ? c : gh - 1)];
+    }
   };
   auto mask_g = [&](int64_t t) {
     const int64_t row0 = t * 16;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) gq[ks] *= opaque((row0 + c < a.n && 4 * ks + g < A && ks < KS2) ? 1.f : 0.f);
+    if constexpr (RA) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) GB[r] *= opaque((row0 + 4 * g + r < a.n && c < gh) ? 1.f : 0.f);
+      for (int r = 0; r < 4; ++r) GB[r] *= opaque((row0 + 4 * g + r < a.n && c < gh) ? 1.f : 0.f);
+    }
   };
-  // x[row0 + 4 g + r][16 m0 + c] (A operand of gW0; rows past n: any finite value, their
-  // ga1 is 0)
+  // x[row0 + 4 g + r][16 m0 + c] (RB: A operand of gW0; rows past n: any finite value,
+  // their ga1 is 0)
   auto take_x = [&]() {
+    if constexpr (RA) return;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
 #pragma unroll
@@ -268,6 +305,7 @@ __global__ __launch_bounds__(64 * VJP16_WAVES, 1) void mlp_fisher_hyb_kernel(Vjp
     }
   };
   auto load_x = [&](int64_t t) {
+    if constexpr (RA) return;
     const int64_t row0 = t * 16;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -284,16 +322,17 @@ __global__ __launch_bounds__(64 * VJP16_WAVES, 1) void mlp_fisher_hyb_kernel(Vjp
   // at (run * 16 + jj) * 4 with the rows of each 4-row group rotated by k = 2 (q & 1) + h,
   // jj = 4 (j >> 2) + ((j + k) & 3): the T reads below (lane (c, g): run of unit 16 p + c,
   // row 4 g + r) then hit 64 distinct banks.  The rotation is applied on the source side
-  // (an LDS-DMA destination is lane-linear).
-  float* const h1s = sH + (wave - 4) * 2 * VJP16_H1_FLOATS;
-  auto dma_h1 = [&](int64_t t, int b) {
+  // (an LDS-DMA destination is lane-linear).  One buffer per wave: a tile's h1 is all in
+  // registers (read_h1, awaited) before the next tile's DMA is issued.
+  float* const h1s = sH + (wave - 4) * VJP16_H1_FLOATS;
+  auto dma_h1 = [&](int64_t t) {
     const float* ct = a.cache + (t >> 1) * CACHE_TILE_FLOATS + 16 * (int)(t & 1) * 4;
     const int jj = lane & 15;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int run = 4 * i + (lane >> 4), sq = run >> 1, hh = run & 1, k = 2 * (sq & 1) + hh;
       const int j = 4 * (jj >> 2) + ((jj - k) & 3);
-      glds16(ct + (sq * 64 + 32 * hh + j) * 4, h1s + b * VJP16_H1_FLOATS + i * 256);
+      glds16(ct + (sq * 64 + 32 * hh + j) * 4, h1s + i * 256);
     }
   };
   // lane parts of the T read offsets: run bits from c, rotated row 4 g + ((r + (c >> 2)) & 3)
@@ -301,12 +340,13 @@ __global__ __launch_bounds__(64 * VJP16_WAVES, 1) void mlp_fisher_hyb_kernel(Vjp
 #pragma unroll
   for (int r = 0; r < 4; ++r)
     offH[r] = ((c >> 3) * 2 + ((c >> 2) & 1)) * 64 + 16 * g + 4 * ((r + (c >> 2)) & 3) + (c & 3);
-  auto read_h1 = [&](int b, int nt) {
-    const float* p = h1s + b * VJP16_H1_FLOATS + (nt >> 1) * 512 + (nt & 1) * 256;
+  auto read_h1 = [&](int nt) {
+    const float* p = h1s + (nt >> 1) * 512 + (nt & 1) * 256;
     h1T[nt] = f32x4{p[offH[0]], p[offH[1]], p[offH[2]], p[offH[3]]};
   };
   // column O reads 1 (a ones column: gW0's row O is the bias gradient sum_rows ga1)
   auto mask_x = [&]() {
+    if constexpr (RA) return;
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -316,61 +356,63 @@ __global__ __launch_bounds__(64 * VJP16_WAVES, 1) void mlp_fisher_hyb_kernel(Vjp
         xA[m0][r] = xv;
       }
   };
-  int buf = 0;
   // one 16-row tile t, the loads of tile tn issued under its chain
   auto vjp_tile = [&](int64_t t, int64_t tn) {
     load_g_mbox(t);
     mask_g(t);
     // ---- gh2 in both layouts (K = head outputs), then ga2 = gh2 (1 - h2^2)
-    f32x4 ga2R[4], ga2T[4];
+    //      in the role's layout (RB: R, RA: T)
+    f32x4 ga2[4];
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
       const float w = w2frag(nt, 0);
-      ga2R[nt] = MFMA16(w, gq[0], zero4);
-      ga2T[nt] = MFMA16(gq[0], w, zero4);
+      ga2[nt] = RB ? MFMA16(w, gq[0], zero4) : MFMA16(gq[0], w, zero4);
     }
     if (KS2 > 1) {
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) {
         const float w = w2frag(nt, 1);
-        ga2R[nt] = MFMA16(w, gq[1], ga2R[nt]);
-        ga2T[nt] = MFMA16(gq[1], w, ga2T[nt]);
+        ga2[nt] = RB ? MFMA16(w, gq[1], ga2[nt]) : MFMA16(gq[1], w, ga2[nt]);
       }
     }
-    // gW2 += h2_T^T G  (k-step r: rows 4 g + r)
+    if constexpr (RA) {
+      // gW2 += h2_T^T G  (k-step r: rows 4 g + r)
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
+      for (int r = 0; r < 4; ++r)
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt) gW2[nt] = MFMA16(h2T[nt][r], GB[r], gW2[nt]);
+        for (int nt = 0; nt < 4; ++nt) gW2[nt] = MFMA16(h2T[nt][r], GB[r], gW2[nt]);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) pG += GB[r];
+      for (int r = 0; r < 4; ++r) pG += GB[r];
+    }
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        ga2R[nt][r] *= dtanh(h2R[nt][r]);
-        ga2T[nt][r] *= dtanh(h2T[nt][r]);
-      }
+      for (int r = 0; r < 4; ++r) ga2[nt][r] *= dtanh(RB ? h2R[nt][r] : h2T[nt][r]);
+    if constexpr (RA) {
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt) pb1[nt] += (ga2T[nt][0] + ga2T[nt][1]) + (ga2T[nt][2] + ga2T[nt][3]);
+      for (int nt = 0; nt < 4; ++nt) pb1[nt] += (ga2[nt][0] + ga2[nt][1]) + (ga2[nt][2] + ga2[nt][3]);
+    }
     __builtin_amdgcn_sched_barrier(0);
-    // ---- gh1_T = ga2_R . W1^T (K = units, k-step (mt, r)) interleaved with
-    //      gW1 += h1_T^T ga2_T (K = rows): independent chains, one MFMA stream
+    // ---- RB: gh1_T = ga2_R . W1^T (K = units, k-step (mt, r));
+    //      RA: gW1 += h1_T^T ga2_T (K = rows)
     f32x4 g1T[4] = {zero4, zero4, zero4, zero4};
     // this tile's h1 (its DMA was issued with the loads phase 1 waited for): all of it is
-    // read before the next tile's DMA is issued
+    // read (RA: group by group in the gW1 loop), and has arrived, before the next tile's DMA
+    // into the same buffer is issued
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if constexpr (RB) {
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt) read_h1(buf, nt);
+      for (int nt = 0; nt < 4; ++nt) read_h1(nt);
+    }
     {
-      // gW1 += h1_T^T ga2_T first (ga2_T's registers are free after it): K = 16 rows, two
-      // part products per MFMA
-      {
+      // gW1 += h1_T^T ga2_T: K = 16 rows, two part products per MFMA
+      if constexpr (RA) {
         bf16x16 gw[4];
 #pragma unroll
-        for (int nt = 0; nt < 4; ++nt) gw[nt] = split4w(ga2T[nt]);
+        for (int nt = 0; nt < 4; ++nt) gw[nt] = split4w(ga2[nt]);
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
+          read_h1(mt);
           const bf16x16 hw = split4w(h1T[mt]);
 #pragma unroll
           for (int nt = 0; nt < 4; ++nt) {
@@ -381,17 +423,19 @@ __global__ __launch_bounds__(64 * VJP16_WAVES, 1) void mlp_fisher_hyb_kernel(Vjp
         }
       }
       __builtin_amdgcn_sched_barrier(0);
-      // the next tile's h2 / x / h1 loads, under the gh1 chain
+      // the next tile's h2 / x / h1 loads (RB: under the gh1 chain); h1T is in registers
       load_h2(tn);
       load_x(tn);
-      dma_h1(tn, buf ^ 1);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      dma_h1(tn);
       __builtin_amdgcn_sched_barrier(0);
       // gh1_T = ga2_R W1^T: two k-steps of 32 units, six part products each (smallest first)
+      if constexpr (RB) {
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         bf16x4 pa[3], pb[3];
-        split4(ga2R[2 * s], pa);
-        split4(ga2R[2 * s + 1], pb);
+        split4(ga2[2 * s], pa);
+        split4(ga2[2 * s + 1], pb);
         const bf16x8 A0 = cat4(pa[0], pb[0]), A1 = cat4(pa[1], pb[1]), A2 = cat4(pa[2], pb[2]);
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
@@ -405,24 +449,26 @@ __global__ __launch_bounds__(64 * VJP16_WAVES, 1) void mlp_fisher_hyb_kernel(Vjp
           g1T[nt] = MFMAB16(A0, B0, g1T[nt]);
         }
       }
+      }
     }
-    // ---- ga1 = gh1 (1 - h1^2) in T;  gW0 += x^T ga1
+    if constexpr (RB) {
+      // ---- ga1 = gh1 (1 - h1^2) in T;  gW0 += x^T ga1
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
+      for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) g1T[nt][r] *= dtanh(h1T[nt][r]);
-    mask_x();
+        for (int r = 0; r < 4; ++r) g1T[nt][r] *= dtanh(h1T[nt][r]);
+      mask_x();
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
+      for (int r = 0; r < 4; ++r)
 #pragma unroll
-      for (int m0 = 0; m0 < MT0; ++m0)
+        for (int m0 = 0; m0 < MT0; ++m0)
 #pragma unroll
-        for (int nt = 0; nt < 4; ++nt) gW0[m0][nt] = MFMA16(xA[m0][r], g1T[nt][r], gW0[m0][nt]);
-    take_x();
-    buf ^= 1;
+          for (int nt = 0; nt < 4; ++nt) gW0[m0][nt] = MFMA16(xA[m0][r], g1T[nt][r], gW0[m0][nt]);
+      take_x();
+    }
   };
   {
-    const int vw = wave - 4;
+    const int vw = (wave - 4) & 3;  // the producer wave whose tiles this wave takes
     int64_t T = (int64_t)blockIdx.x * 4 + vw;
     // the first tile's inputs: before round 0's barrier (PROD 0: the cache is read-only
     // here), or after it (PROD 1: the producer wrote them in round 0)
@@ -430,7 +476,7 @@ __global__ __launch_bounds__(64 * VJP16_WAVES, 1) void mlp_fisher_hyb_kernel(Vjp
       if (r == LAG - 1 && T < nt32) {
         load_h2(2 * T);
         load_x(2 * T);
-        dma_h1(2 * T, 0);
+        dma_h1(2 * T);
         take_x();
       }
       fused_barrier();  // round r: the producer waves fill slot r
@@ -447,14 +493,28 @@ __global__ __launch_bounds__(64 * VJP16_WAVES, 1) void mlp_fisher_hyb_kernel(Vjp
     }
   }
 
+  // ---- the four VJP wave pairs store one slab row each (mrl_slab_rows = 4 per block):
+  //      RA its gW1 / gW2 / b1 / b2 / logstd entries, RB gW0 / b0 -- together all P
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last (unused) h1 DMA has landed
+  float* out = a.slab + ((int64_t)blockIdx.x * 4 + ((wave - 4) & 3)) * d.P;
+  if constexpr (RB) {
+    // gW0 [i][u]: i = 16 m0 + 4 g + r, u = 16 nt + c; row O (the ones column) is b0's
+#pragma unroll
+    for (int m0 = 0; m0 < MT0; ++m0)
+#pragma unroll
+      for (int n = 0; n < 4; ++n)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int i = 16 * m0 + 4 * g + r;
+          if (i < d.O) out[d.tW0 + i * HID + 16 * n + c] = gW0[m0][n][r];
+          else if (i == d.O) out[d.tb0 + 16 * n + c] = gW0[m0][n][r];
+        }
+    return;
+  }
   // ---- bias / logstd partials: sum over the four lane groups (rows)
 #pragma unroll
   for (int nt = 0; nt < 4; ++nt) pb1[nt] = xor32_add(xor16_add(pb1[nt]));
   pG = xor32_add(xor16_add(pG));
-
-  // ---- the four VJP waves store one slab row each (mrl_slab_rows = 4 per block)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last (unused) h1 DMA has landed
-  float* out = a.slab + ((int64_t)blockIdx.x * 4 + (wave - 4)) * d.P;
   // gW1 [in][out]: in = 16 mt + 4 g + r, out = 16 nt + c
 #pragma unroll
   for (int m = 0; m < 4; ++m)
@@ -468,23 +528,15 @@ __global__ __launch_bounds__(64 * VJP16_WAVES, 1) void mlp_fisher_hyb_kernel(Vjp
 #pragma unroll
     for (int r = 0; r < 4; ++r)
       if (c < A) out[d.tW2 + (16 * n + 4 * g + r) * A + c] = gW2[n][r];
-  // gW0 [i][u]: i = 16 m0 + 4 g + r, u = 16 nt + c; row O (the ones column) is b0's
-#pragma unroll
-  for (int m0 = 0; m0 < MT0; ++m0)
-#pragma unroll
-    for (int n = 0; n < 4; ++n)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = 16 * m0 + 4 * g + r;
-        if (i < d.O) out[d.tW0 + i * HID + 16 * n + c] = gW0[m0][n][r];
-        else if (i == d.O) out[d.tb0 + 16 * n + c] = gW0[m0][n][r];
-      }
   if (g == 0) {
 #pragma unroll
     for (int n = 0; n < 4; ++n) out[d.tb1 + 16 * n + c] = pb1[n];
     if (c < A) out[d.tb2 + c] = pG;
     else if (c < gh) out[d.tls + (c - A)] = pG;
   }
+  };
+  if (wave < 4 + HYB_VJP_WAVES / 2) vjp_role(std::false_type{});
+  else vjp_role(std::true_type{});
 }
 
 }  // namespace mrl
@@ -522,13 +574,13 @@ static void hyb_args(const mrl_mlp_desc* d, const float* theta, const float* ima
   fz.img_s = image_s;
 }
 
-// the VJP's grid and slab rows (mrl_mlp_slab_rows): one slab row per VJP wave (PROD 1: and
-// one partial row (surr, kl, ent, 0) per producer wave -- the same count); dynamic LDS:
+// the VJP's grid and slab rows (mrl_mlp_slab_rows): one slab row per VJP wave pair (PROD 1:
+// and one partial row (surr, kl, ent, 0) per producer wave -- the same count); dynamic LDS:
 // the split images of theta and (PROD 0) of the tangent
 template <int PROD>
 static int launch_hyb(const mrl_mlp_desc* d, const VjpArgs& a, const FisherFusedIn& fz, const float* image,
                       const int32_t* skip, void* stream, const char* what) {
-  const dim3 grid(grid_blocks(a.n, scaled_cap(VJP_MAX_BLOCKS, desc_cus(d)))), blk(64 * VJP16_WAVES);
+  const dim3 grid(grid_blocks(a.n, scaled_cap(VJP_MAX_BLOCKS, desc_cus(d)))), blk(64 * HYB_WAVES);
   const size_t shm = (size_t)split_fwd_words(fz.rb) * 4 * (PROD == 0 ? 2 : 1);
   hipStream_t s = (hipStream_t)stream;
   switch (static_shape_of(d, false)) {
@@ -551,9 +603,11 @@ int32_t mrl_mlp_fisher_hyb_fits(const mrl_mlp_desc* d) {
   if (m.O > 16 || m.O % 16 == 0) return 0;
   // the static shapes only (the run-time-shape instantiation spills at 256 registers)
   if (static_shape_of(d, false) == 0) return 0;
-  const size_t lds = (size_t)split_fwd_words(bf16_dims(d->n_in, d->n_out)) * 4 * 2 + 2 * 4 * 64 * 4 +
-                     4 * 2 * VJP16_H1_FLOATS * 4 + 2 * 4 * 3 * 64 * 16 + 2 * 4 * 32 * MBOX_GH * 4;
-  return lds <= 160 * 1024 ? 1 : 0;
+  // the larger of the two instantiations: the product (two images, two mailbox slots) and
+  // the gradient (one image, three slots)
+  const size_t image = (size_t)split_fwd_words(bf16_dims(d->n_in, d->n_out)) * 4;
+  const size_t prod = 2 * image + hyb_static_lds(2), grad = image + hyb_static_lds(3);
+  return (prod > grad ? prod : grad) <= 160 * 1024 ? 1 : 0;
 }
 
 int mrl_mlp_fisher_hyb(const mrl_mlp_desc* d, const float* theta, const float* image, const float* image_s,

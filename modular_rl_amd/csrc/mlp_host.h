@@ -21,7 +21,12 @@ constexpr int ROWS_BLOCK = 256;
 #endif
 constexpr int ROWS_MAX_BLOCKS = MRL_ROWS_MAX_BLOCKS;
 constexpr int VJP_MAX_BLOCKS = 256;
-constexpr int VJP16_WAVES = 8;  // waves per block of mlp_vjp16_kernel and mlp_fisher_hyb_kernel
+constexpr int VJP16_WAVES = 8;  // waves per block of mlp_vjp16_kernel
+// mlp_fisher_hyb_kernel: three waves per SIMD -- four producer waves and the VJP of their
+// tiles on eight (four accumulate gW1 / gW2 / b1 / b2 / logstd, four gW0 / b0); a VJP pair
+// fills one slab row, so the kernel keeps four slab rows and four partial rows per block
+constexpr int HYB_WAVES = 12;
+constexpr int HYB_VJP_WAVES = 8;
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
