@@ -1,5 +1,6 @@
 // The C ABI of the fused 64-wide MLP path on v_mfma_f32_32x32x2_f32 (exact fp32), its
-// small kernels (image pack, slab reductions, probtype rows) and the line-search scorer.
+// small kernels (image pack, probtype rows) and the line-search scorer (the slab
+// reductions it and every gradient pass end with are vector_ops.hip's).
 // The big kernels live in their own units:
 //
 //   mlp_rows_vjp.hip  mlp_rows_kernel<EPI>  forward (+ JVP) of a 32-row tile per wave with
@@ -41,63 +42,12 @@ int hip_check(hipError_t e, const char* what) {
   return OK;
 }
 
-// ------------------------------------------------------------------ pack / reduce
+// ------------------------------------------------------------------ pack
 __global__ void mlp_pack_kernel(MlpDims d, const float* __restrict__ th, float* __restrict__ image, int count,
                                 const int32_t* __restrict__ skip) {
   if (skip != nullptr && *skip != 0) return;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < count) image[i] = image_value(d, th, i);
-}
-
-// RG row groups of 64 columns per block (blockDim = 64 * RG); group g sums rows
-// g, g + RG, ... with 8 independent accumulators (8 loads in flight per lane), then
-// the RG group sums are added in a fixed pairwise order
-template <class T, class O, int RG = 4>
-__global__ void reduce_rows_kernel(const T* __restrict__ slab, int64_t rows, int64_t cols, O* __restrict__ out,
-                                   const int32_t* __restrict__ skip) {
-  __shared__ double part[RG][64];
-  if (skip != nullptr && *skip != 0) return;
-  const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
-  const int64_t col = (int64_t)blockIdx.x * 64 + c;
-  double s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (col < cols) {
-    int64_t r = g;
-    for (; r + 7 * RG < rows; r += 8 * RG) {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) s[q] += (double)slab[(r + RG * q) * cols + col];
-    }
-    for (; r < rows; r += RG) s[0] += (double)slab[r * cols + col];
-  }
-  part[g][c] = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
-  __syncthreads();
-  if constexpr (RG == 4) {
-    if (g == 0 && col < cols) out[col] = (O)(((part[0][c] + part[1][c]) + part[2][c]) + part[3][c]);
-  } else {
-#pragma unroll
-    for (int w = RG / 2; w >= 1; w >>= 1) {
-      if (g < w) part[g][c] += part[g + w][c];
-      __syncthreads();
-    }
-    if (g == 0 && col < cols) out[col] = (O)part[0][c];
-  }
-}
-
-// few columns (per-wave loss partials): one block per column, 256 threads over rows
-template <class T, class O>
-__global__ void reduce_rows_narrow_kernel(const T* __restrict__ slab, int64_t rows, int64_t cols, O* __restrict__ out,
-                                          const int32_t* __restrict__ skip) {
-  __shared__ double red[256];
-  if (skip != nullptr && *skip != 0) return;
-  const int64_t col = blockIdx.x;
-  double s = 0.0;
-  for (int64_t r = threadIdx.x; r < rows; r += 256) s += (double)slab[r * cols + col];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[col] = (O)red[0];
 }
 
 // per-row probtype values on probability rows (mrl_probtype_rows): the helpers the
@@ -318,33 +268,6 @@ int mrl_probtype_rows(int32_t head, int32_t k, int64_t n, const float* prob, con
   hipLaunchKernelGGL(probtype_rows_kernel, dim3(std::min<int64_t>(ceil_div(n, 256), 2048)), dim3(256), 0, (hipStream_t)stream, (int)head, (int)k, n,
                      prob, prob2, x, loglik, kl, ent);
   return hip_check(hipGetLastError(), "mrl_probtype_rows");
-}
-
-int mrl_reduce_rows_f32(const float* slab, int64_t rows, int64_t cols, float* out, const int32_t* skip, void* stream) {
-  if (!slab || !out) return fail(E_ARG, "null pointer");
-  if (cols <= 0) return OK;
-  // tall slabs (the fused VJP's per-wave rows: 1,024 x 5,126 for Hopper, only 81
-  // column blocks wide): 16 row groups (1,024 threads) so the row split fills the chip;
-  // short wide ones (the layered GEMMs' split-K slabs, 64 rows) keep 4 groups
-  if (rows >= 256)
-    hipLaunchKernelGGL((reduce_rows_kernel<float, float, 16>), dim3(ceil_div(cols, 64)), dim3(1024), 0,
-                       (hipStream_t)stream, slab, rows, cols, out, skip);
-  else
-    hipLaunchKernelGGL((reduce_rows_kernel<float, float, 4>), dim3(ceil_div(cols, 64)), dim3(256), 0,
-                       (hipStream_t)stream, slab, rows, cols, out, skip);
-  return hip_check(hipGetLastError(), "mrl_reduce_rows_f32");
-}
-int mrl_reduce_rows_f64(const double* slab, int64_t rows, int64_t cols, double* out, const int32_t* skip,
-                        void* stream) {
-  if (!slab || !out) return fail(E_ARG, "null pointer");
-  if (cols <= 0) return OK;
-  if (cols <= 16)
-    hipLaunchKernelGGL((reduce_rows_narrow_kernel<double, double>), dim3(cols), dim3(256), 0, (hipStream_t)stream,
-                       slab, rows, cols, out, skip);
-  else
-    hipLaunchKernelGGL((reduce_rows_kernel<double, double>), dim3(ceil_div(cols, 64)), dim3(256), 0,
-                       (hipStream_t)stream, slab, rows, cols, out, skip);
-  return hip_check(hipGetLastError(), "mrl_reduce_rows_f64");
 }
 
 // K line-search candidates of the fused policy scored in one call, read back once by the

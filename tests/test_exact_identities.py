@@ -4,7 +4,7 @@
   multiplies by the exact 2^-k instead.  Both are IEEE operations on the same real value
   x / 2^k, rounded once, so the results are identical -- including quotients in the
   subnormal range, signed zeros, infinities and NaN.
-* scan.hip `gae_full_kernel`: a chunk's multipliers B = (gl*kk)*B over its steps are
+* gae.hip `gae_full_kernel`: a chunk's multipliers B = (gl*kk)*B over its steps are
   gl^L when no step breaks the chunk; the power is formed by the same sequence of
   multiplications, so it equals the per-step product bit for bit (kk in {0, 1}).
 """

@@ -1,4 +1,4 @@
-"""Direct GPU checks of the flat-vector layer (csrc/scan.hip, csrc/mlp_kernels.hip): the slab
+"""Direct GPU checks of the flat-vector layer (csrc/vector_ops.hip, csrc/gae.hip): the slab
 reductions, the moments, the standardisation and the grid-stride elementwise kernels, each
 at the smallest sizes on either side of every branch of its dispatch (row-group switch at
 256 rows, narrow / wide fp64 reduction at 16 columns, unroll trips and tails, one block /
