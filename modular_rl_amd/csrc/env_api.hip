@@ -160,8 +160,7 @@ static int check_env(const char* who, const mrl_rollout_desc* d, const mrl_rollo
   if (!d) what = "null desc";
   else if (!b) what = "null bufs";
   else if (!io) what = "null io";
-  else if (d->env_id != MRL_ENV_CARTPOLE && d->env_id != MRL_ENV_HOPPER && d->env_id != MRL_ENV_HUMANOID)
-    what = "desc.env_id: unknown env";
+  else if (!env_known(d->env_id)) what = "desc.env_id: unknown env";
   else if (d->n_envs <= 0) what = "desc.n_envs <= 0";
   else if (!b->env_state) what = "null bufs.env_state";
   else if (!b->env_int) what = "null bufs.env_int";
@@ -176,7 +175,7 @@ int mrl_env_reset(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, const mr
   RollArgs a = make_args(d, b);
   const dim3 genv((d->n_envs + 63) / 64);
   if (d->env_id == MRL_ENV_HUMANOID) launch_hm_env_reset(a, *io, (hipStream_t)stream);
-  else MRL_DISPATCH_ENV2(d->env_id, env_reset_kernel, genv, dim3(64), 0, (hipStream_t)stream, a, *io);
+  else MRL_DISPATCH_THREAD_ENV(d->env_id, env_reset_kernel, genv, dim3(64), 0, (hipStream_t)stream, a, *io);
   return hip_check(hipGetLastError(), "mrl_env_reset");
 }
 
@@ -192,7 +191,7 @@ int mrl_env_step(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, const mrl
   const int ar = auto_reset != 0;
   const dim3 genv((d->n_envs + 63) / 64);
   if (d->env_id == MRL_ENV_HUMANOID) launch_hm_env_step(a, *io, ar, (hipStream_t)stream);
-  else MRL_DISPATCH_ENV2(d->env_id, env_step_kernel, genv, dim3(64), 0, (hipStream_t)stream, a, *io, ar);
+  else MRL_DISPATCH_THREAD_ENV(d->env_id, env_step_kernel, genv, dim3(64), 0, (hipStream_t)stream, a, *io, ar);
   return hip_check(hipGetLastError(), "mrl_env_step");
 }
 

@@ -235,8 +235,7 @@ extern "C" int mrl_pop_rollout(const mrl_rollout_desc* d, const mrl_rollout_bufs
   else if (!pol) what = "null policy desc";
   else if (!thetas) what = "null thetas";
   else if (!io) what = "null io";
-  else if (d->env_id != MRL_ENV_CARTPOLE && d->env_id != MRL_ENV_HOPPER && d->env_id != MRL_ENV_HUMANOID)
-    what = "desc.env_id: unknown env";
+  else if (!env_known(d->env_id)) what = "desc.env_id: unknown env";
   else if (d->n_envs <= 0) what = "desc.n_envs <= 0";
   else if (!b->env_state) what = "null bufs.env_state";
   else if (!b->env_int) what = "null bufs.env_int";
@@ -249,7 +248,7 @@ extern "C" int mrl_pop_rollout(const mrl_rollout_desc* d, const mrl_rollout_bufs
   }
   if (what) return fail(E_ARG, std::string("mrl_pop_rollout: ") + what);
   if (d->env_id == MRL_ENV_HUMANOID)
-    return fail(E_UNSUPPORTED, "mrl_pop_rollout: Humanoid is not supported (CartPole and Hopper only)");
+    return fail(E_UNSUPPORTED, "mrl_pop_rollout: Humanoid is not supported (the thread-per-env envs only)");
   const EnvInfo ei = env_info(d->env_id);
   const bool gauss = pol->head == MRL_HEAD_GAUSS, softmax = pol->head == MRL_HEAD_SOFTMAX;
   if (pol->n_hidden != HID || pol->n_layers != 2 || pol->n_in != ei.obs || pol->n_out != ei.act ||
@@ -266,6 +265,6 @@ extern "C" int mrl_pop_rollout(const mrl_rollout_desc* d, const mrl_rollout_bufs
   p.io = *io;
   p.limit = d->timestep_limit > 0 && d->timestep_limit < ei.max_steps ? d->timestep_limit : ei.max_steps;
   const dim3 grid((d->n_envs + POP_W - 1) / POP_W);
-  MRL_DISPATCH_ENV2(d->env_id, pop_rollout_kernel, grid, dim3(POP_W), 0, (hipStream_t)stream, a, p);
+  MRL_DISPATCH_THREAD_ENV(d->env_id, pop_rollout_kernel, grid, dim3(POP_W), 0, (hipStream_t)stream, a, p);
   return hip_check(hipGetLastError(), "mrl_pop_rollout");
 }

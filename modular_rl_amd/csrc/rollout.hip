@@ -1051,7 +1051,7 @@ int mrl_rollout_reset(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, void
   if (rc) return rc;
   if (d->env_id == MRL_ENV_HUMANOID) return fail(E_UNSUPPORTED, "Humanoid runs on the layered rollout (mrl_rollout_reset_rows)");
   RollArgs a = make_args(d, b);
-  MRL_DISPATCH_ENV2(d->env_id, rollout_reset_kernel, dim3(a.nb), dim3(RB), 0, (hipStream_t)stream, a);
+  MRL_DISPATCH_THREAD_ENV(d->env_id, rollout_reset_kernel, dim3(a.nb), dim3(RB), 0, (hipStream_t)stream, a);
   return hip_check(hipGetLastError(), "mrl_rollout_reset");
 }
 
@@ -1135,7 +1135,7 @@ int mrl_rollout_run(const mrl_rollout_desc* d, const mrl_mlp_desc* pol, const fl
   // launch made HIP keep a runtime-owned queue that its teardown destroyed after an
   // attached rocprofv3 had finalised: the profiled process crashed at exit.
   const bool bf = d->compute == MRL_COMPUTE_BF16, st = b->stamps != nullptr;
-  dispatch_env2(d->env_id, [&](auto env) {
+  dispatch_thread_env(d->env_id, [&](auto env) {
     dispatch_bool(bf, [&](auto BF) {
       dispatch_bool(st, [&](auto ST) {
         hipLaunchKernelGGL((rollout_persistent_kernel<env(), BF(), ST()>), dim3(a.nb), dim3(RB), 0, s, a, logstd, rimage,
@@ -1156,7 +1156,7 @@ int mrl_rollout_step(const mrl_rollout_desc* d, const mrl_mlp_desc* pol, const f
   const float* logstd = pol->head == MRL_HEAD_GAUSS ? theta + md.tls : nullptr;
   const bool bf = d->compute == MRL_COMPUTE_BF16;
   hipStream_t s = (hipStream_t)stream;
-  dispatch_env2(d->env_id, [&](auto env) {
+  dispatch_thread_env(d->env_id, [&](auto env) {
     dispatch_bool(bf, [&](auto BF) {
       hipLaunchKernelGGL((rollout_step_kernel<env(), BF()>), dim3(a.nb), dim3(RB), 0, s, a, logstd, rimage, t);
     });

@@ -9,6 +9,7 @@
 
 #include "../../include/mrl_hip.h"
 #include "envs.h"
+#include "envs_classic.h"
 #include "mlp_device.h"
 
 namespace mrl {
@@ -107,13 +108,74 @@ struct EnvC<MRL_ENV_HUMANOID> {  // stepped by the wave-per-env kernels (hm_*_ke
   __device__ static void obs_out(const double*, Out) {}
 };
 
+// the classic-control envs (envs_classic.h): a thread steps an env whole, so the four rows
+// of the fused step all step it identically, as CartPole's do
+template <>
+struct EnvC<MRL_ENV_PENDULUM> {
+  static constexpr int NS = PD_NS, OBS = PD_OBS, ACT = PD_ACT, DISCRETE = 0, MAX_STEPS = 200, NU = 2, OBS_SLOTS = 0;
+  __device__ static void reset(const double* u, double* s) { pendulum_reset(u, s); }
+  __device__ static void obs(const double* s, double* o) { pendulum_obs(s, o); }
+  __device__ static void step_disc(double*, int, double&, bool&) {}
+  __device__ static void step_cont(double* s, const float* a, double& rew, bool& done) { pendulum_step(s, a, rew, done); }
+  __device__ static void step_cont_quad(double* s, const float* a, double& rew, bool& done, int, const double*) {
+    pendulum_step(s, a, rew, done);
+  }
+  template <class Out>
+  __device__ static void obs_out(const double* s, Out out) {
+    double o[OBS];
+    pendulum_obs(s, o);
+#pragma unroll
+    for (int k = 0; k < OBS; ++k) out(k, o[k]);
+  }
+};
+template <>
+struct EnvC<MRL_ENV_MOUNTAINCAR> {
+  static constexpr int NS = MC_NS, OBS = MC_OBS, ACT = 3, DISCRETE = 1, MAX_STEPS = 200, NU = 2, OBS_SLOTS = 0;
+  __device__ static void reset(const double* u, double* s) { mountaincar_reset(u, s); }
+  __device__ static void obs(const double* s, double* o) { mountaincar_obs(s, o); }
+  __device__ static void step_disc(double* s, int a, double& rew, bool& done) { mountaincar_step(s, a, rew, done); }
+  __device__ static void step_cont(double*, const float*, double&, bool&) {}
+  __device__ static void step_cont_quad(double*, const float*, double&, bool&, int, const double*) {}
+  template <class Out>
+  __device__ static void obs_out(const double* s, Out out) {
+    double o[OBS];
+    mountaincar_obs(s, o);
+#pragma unroll
+    for (int k = 0; k < OBS; ++k) out(k, o[k]);
+  }
+};
+template <>
+struct EnvC<MRL_ENV_ACROBOT> {
+  static constexpr int NS = AC_NS, OBS = AC_OBS, ACT = 3, DISCRETE = 1, MAX_STEPS = 500, NU = 4, OBS_SLOTS = 0;
+  __device__ static void reset(const double* u, double* s) { acrobot_reset(u, s); }
+  __device__ static void obs(const double* s, double* o) { acrobot_obs(s, o); }
+  __device__ static void step_disc(double* s, int a, double& rew, bool& done) { acrobot_step(s, a, rew, done); }
+  __device__ static void step_cont(double*, const float*, double&, bool&) {}
+  __device__ static void step_cont_quad(double*, const float*, double&, bool&, int, const double*) {}
+  template <class Out>
+  __device__ static void obs_out(const double* s, Out out) {
+    double o[OBS];
+    acrobot_obs(s, o);
+#pragma unroll
+    for (int k = 0; k < OBS; ++k) out(k, o[k]);
+  }
+};
+
 struct EnvInfo {
   int ns, obs, act, discrete, max_steps;
 };
 __host__ __device__ inline EnvInfo env_info(int id) {
   if (id == MRL_ENV_CARTPOLE) return EnvInfo{CP_NS, CP_OBS, 2, 1, 200};
   if (id == MRL_ENV_HUMANOID) return EnvInfo{HM_NS, HM_OBS, HM_ACT, 0, 1000};
+  if (id == MRL_ENV_PENDULUM) return EnvInfo{PD_NS, PD_OBS, PD_ACT, 0, 200};
+  if (id == MRL_ENV_MOUNTAINCAR) return EnvInfo{MC_NS, MC_OBS, 3, 1, 200};
+  if (id == MRL_ENV_ACROBOT) return EnvInfo{AC_NS, AC_OBS, 3, 1, 500};
   return EnvInfo{HP_NS, HP_OBS, HP_ACT, 0, 1000};
+}
+// the ids the entry points take (MRL_ENV_*; 3 is not one)
+__host__ __device__ inline bool env_known(int id) {
+  return id == MRL_ENV_CARTPOLE || id == MRL_ENV_HOPPER || id == MRL_ENV_HUMANOID || id == MRL_ENV_PENDULUM ||
+         id == MRL_ENV_MOUNTAINCAR || id == MRL_ENV_ACROBOT;
 }
 __host__ __device__ inline int filt_doubles(int obs) { return 2 + 2 * (obs + 1); }
 

@@ -13,8 +13,7 @@ namespace mrl {
 
 inline int check_roll(const mrl_rollout_desc* d, const mrl_rollout_bufs* b) {
   if (!d || !b) return fail(E_ARG, "null desc/bufs");
-  if (d->env_id != MRL_ENV_CARTPOLE && d->env_id != MRL_ENV_HOPPER && d->env_id != MRL_ENV_HUMANOID)
-    return fail(E_UNSUPPORTED, "unknown env_id");
+  if (!env_known(d->env_id)) return fail(E_UNSUPPORTED, "unknown env_id");
   if (d->n_envs <= 0 || d->horizon <= 0 || d->timestep_limit <= 0) return fail(E_ARG, "bad sizes");
   if (d->compute != MRL_COMPUTE_F32 && d->compute != MRL_COMPUTE_BF16) return fail(E_ARG, "bad compute");
   if (!b->env_state || !b->env_int || !b->filter_state || !b->records || !b->iteration) return fail(E_ARG, "null state");
@@ -56,23 +55,30 @@ inline int check_fused_run(const mrl_rollout_desc* d, const mrl_mlp_desc* pol, c
 }
 
 // ------------------------------------------------------------------ dispatch
-// A kernel template <int ENV> launched for a run-time env id: all three envs ...
-#define MRL_DISPATCH_ENV(id, KERNEL, ...)                                                    \
-  do {                                                                                      \
-    if ((id) == MRL_ENV_CARTPOLE) hipLaunchKernelGGL(KERNEL<MRL_ENV_CARTPOLE>, __VA_ARGS__); \
-    else if ((id) == MRL_ENV_HOPPER) hipLaunchKernelGGL(KERNEL<MRL_ENV_HOPPER>, __VA_ARGS__); \
-    else hipLaunchKernelGGL(KERNEL<MRL_ENV_HUMANOID>, __VA_ARGS__);                         \
+// A kernel template <int ENV> launched for a run-time env id: every env ...
+#define MRL_DISPATCH_ENV(id, KERNEL, ...)                                                          \
+  do {                                                                                            \
+    if ((id) == MRL_ENV_CARTPOLE) hipLaunchKernelGGL(KERNEL<MRL_ENV_CARTPOLE>, __VA_ARGS__);       \
+    else if ((id) == MRL_ENV_HOPPER) hipLaunchKernelGGL(KERNEL<MRL_ENV_HOPPER>, __VA_ARGS__);      \
+    else if ((id) == MRL_ENV_PENDULUM) hipLaunchKernelGGL(KERNEL<MRL_ENV_PENDULUM>, __VA_ARGS__);  \
+    else if ((id) == MRL_ENV_MOUNTAINCAR)                                                         \
+      hipLaunchKernelGGL(KERNEL<MRL_ENV_MOUNTAINCAR>, __VA_ARGS__);                               \
+    else if ((id) == MRL_ENV_ACROBOT) hipLaunchKernelGGL(KERNEL<MRL_ENV_ACROBOT>, __VA_ARGS__);    \
+    else hipLaunchKernelGGL(KERNEL<MRL_ENV_HUMANOID>, __VA_ARGS__);                               \
   } while (0)
 
-// ... or the two that are stepped by a thread per env (CartPole, Hopper; the callers have
-// turned Humanoid away or launch its wave-per-env kernel): f(integral_constant<int, ENV>)
+// ... or those that are stepped by a thread per env (all but Humanoid: the callers have
+// turned it away or launch its wave-per-env kernel): f(integral_constant<int, ENV>)
 template <class F>
-inline void dispatch_env2(int id, F&& f) {
+inline void dispatch_thread_env(int id, F&& f) {
   if (id == MRL_ENV_CARTPOLE) f(std::integral_constant<int, MRL_ENV_CARTPOLE>{});
+  else if (id == MRL_ENV_PENDULUM) f(std::integral_constant<int, MRL_ENV_PENDULUM>{});
+  else if (id == MRL_ENV_MOUNTAINCAR) f(std::integral_constant<int, MRL_ENV_MOUNTAINCAR>{});
+  else if (id == MRL_ENV_ACROBOT) f(std::integral_constant<int, MRL_ENV_ACROBOT>{});
   else f(std::integral_constant<int, MRL_ENV_HOPPER>{});
 }
-#define MRL_DISPATCH_ENV2(id, KERNEL, ...) \
-  dispatch_env2((id), [&](auto env) { hipLaunchKernelGGL(KERNEL<env()>, __VA_ARGS__); })
+#define MRL_DISPATCH_THREAD_ENV(id, KERNEL, ...) \
+  dispatch_thread_env((id), [&](auto env) { hipLaunchKernelGGL(KERNEL<env()>, __VA_ARGS__); })
 
 // a run-time flag as a template argument: f(std::true_type) or f(std::false_type)
 template <class F>

@@ -511,7 +511,7 @@ int mrl_rollout_reset_rows(const mrl_rollout_desc* d, const mrl_rollout_bufs* b,
   const dim3 genv((d->n_envs + 63) / 64), gpart(a.nb, (D + LCOLS - 1) / LCOLS);
   hipStream_t s = (hipStream_t)stream;
   if (d->env_id == MRL_ENV_HUMANOID) MRL_LAUNCH_HM(hm_reset_kernel, hm_lds_state, d->n_envs, s, a);
-  else MRL_DISPATCH_ENV2(d->env_id, lrollout_reset_kernel, genv, dim3(64), 0, s, a);
+  else MRL_DISPATCH_THREAD_ENV(d->env_id, lrollout_reset_kernel, genv, dim3(64), 0, s, a);
   hipLaunchKernelGGL(lrollout_partials_kernel, gpart, dim3(RB), 0, s, a, D, 0, 0);
   return hip_check(hipGetLastError(), "mrl_rollout_reset_rows");
 }
@@ -547,7 +547,7 @@ static int rollout_act(const mrl_rollout_desc* d, int32_t head, int32_t n_out, c
   const dim3 genv((d->n_envs + 63) / 64), gpart(a.nb, (D + LCOLS - 1) / LCOLS);
   hipStream_t s = (hipStream_t)stream;
   if (d->env_id == MRL_ENV_HUMANOID) MRL_LAUNCH_HM(hm_act_kernel, hm_lds_bytes, d->n_envs, s, a, z, hr, logstd, t);
-  else MRL_DISPATCH_ENV2(d->env_id, lrollout_act_kernel, genv, dim3(64), 0, s, a, z, logstd, t);
+  else MRL_DISPATCH_THREAD_ENV(d->env_id, lrollout_act_kernel, genv, dim3(64), 0, s, a, z, logstd, t);
   hipLaunchKernelGGL(lrollout_partials_kernel, gpart, dim3(RB), 0, s, a, D, (t + 1) & 1, 1);
   return hip_check(hipGetLastError(), "mrl_rollout_act");
 }

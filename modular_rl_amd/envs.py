@@ -1,6 +1,6 @@
 """Env registry for the device env steppers (replaces ``gym.envs.make``, run_pg.py:85).
 
-The dynamics live in ``csrc/envs.h`` / ``csrc/humanoid.h`` and run inside the rollout
+The dynamics live in ``csrc/envs.h`` / ``csrc/envs_classic.h`` / ``csrc/humanoid.h`` and run inside the rollout
 kernels; this module describes them with gym-compatible spaces / spec so that
 ``TrpoAgent(env.observation_space, env.action_space, cfg)`` and
 ``env.spec.max_episode_steps`` (run_pg.py:103-108) work unchanged, and ``VecEnv`` steps
@@ -11,6 +11,9 @@ them with the caller's own actions (``mrl_env_reset`` / ``mrl_env_step``).
   MuJoCo is not available, so its dynamics are a stand-in.
 * ``Humanoid-v2`` -- Humanoid-v2-SHAPED surrogate (obs 376, act 17 in [-0.4, 0.4],
   TimeLimit 1000); its 376-d obs needs the layered rollout (collector.py).
+* ``Pendulum-v0``, ``MountainCar-v0``, ``Acrobot-v1`` -- gym's classic-control equations
+  (``csrc/envs_classic.h``): a 1-d torque in [-2, 2] (TimeLimit 200, never done by itself),
+  three discrete actions (TimeLimit 200) and three discrete torques (TimeLimit 500).
 """
 import ctypes
 
@@ -50,6 +53,10 @@ REGISTRY = {
     "Hopper-v2": dict(kind=_lib.ENV_HOPPER, obs=11, act=3, discrete=False, max_steps=1000, obs_high=np.inf),
     "Humanoid-v2": dict(kind=_lib.ENV_HUMANOID, obs=376, act=17, discrete=False, max_steps=1000, obs_high=np.inf,
                         act_high=0.4),
+    "Pendulum-v0": dict(kind=_lib.ENV_PENDULUM, obs=3, act=1, discrete=False, max_steps=200, obs_high=np.inf,
+                        act_high=2.0),
+    "MountainCar-v0": dict(kind=_lib.ENV_MOUNTAINCAR, obs=2, act=3, discrete=True, max_steps=200, obs_high=np.inf),
+    "Acrobot-v1": dict(kind=_lib.ENV_ACROBOT, obs=6, act=3, discrete=True, max_steps=500, obs_high=np.inf),
 }
 
 
