@@ -5,7 +5,8 @@ CSRC := modular_rl_amd/csrc
 SRCS := $(CSRC)/mlp_kernels.hip $(CSRC)/mlp_rows_vjp.hip $(CSRC)/mlp_vjp16.hip $(CSRC)/mlp_fisher.hip \
   $(CSRC)/mlp_bf16.hip $(CSRC)/mlp_split.hip $(CSRC)/gae.hip $(CSRC)/cg.hip $(CSRC)/episode_stats.hip \
   $(CSRC)/vector_ops.hip $(CSRC)/rollout.hip $(CSRC)/rollout_layered.hip \
-  $(CSRC)/env_api.hip $(CSRC)/gemm.hip $(CSRC)/gemm_bf16.hip $(CSRC)/cem.hip \
+  $(CSRC)/env_api.hip $(CSRC)/gemm.hip $(CSRC)/gemm_bf16.hip $(CSRC)/gemm_bf16_big.hip \
+  $(CSRC)/gemm_bf16_stream.hip $(CSRC)/gemm_bf16_tn.hip $(CSRC)/cem.hip \
   $(CSRC)/pop_rollout.hip $(CSRC)/runtime.hip
 HDRS := $(wildcard $(CSRC)/*.h) include/mrl_hip.h
 OBJS := $(patsubst $(CSRC)/%.hip,build/%.o,$(SRCS))

@@ -244,7 +244,8 @@ int mrl_gemm(const mrl_gemm_desc* g, const int32_t* skip, void* stream);
  * or fewer than 160 128x128 blocks) or 128 (0 for an empty product); host-only query */
 int32_t mrl_gemm_tile_n(const mrl_gemm_desc* g);
 
-/* bf16-operand GEMMs of the layered path's bf16 mode (csrc/gemm_bf16.hip): operands in
+/* bf16-operand GEMMs of the layered path's bf16 mode (csrc/gemm_bf16.hip and its
+ * kernel units gemm_bf16_big.hip, gemm_bf16_stream.hip, gemm_bf16_tn.hip): operands in
  * HBM as bf16 (a bf16 tape and packed bf16 weight images), f32 accumulation.  The
  * reference interface they serve is the same as mrl_gemm's (Keras Dense layers,
  * agentzoo.py:34-48, and their Theano gradients, trpo.py:40-47). */

@@ -390,7 +390,7 @@ class LayeredMlpNet:
         self.desc = None
         self._tape = None  # (key, X, ldx, [H_1..H_L], Z)
         # bf16 mode keeps the tape, the JVP / gradient chains and packed weight images in
-        # bf16 and runs the large-M passes on the bf16-operand GEMMs (csrc/gemm_bf16.hip);
+        # bf16 and runs the large-M passes on the bf16-operand GEMMs (csrc/gemm_bf16*.hip);
         # the rollout's per-step forward (forward_rows) stays on mrl_gemm, except the
         # Humanoid step's hidden layers (forward_hidden_rows_b16)
         # (hidden widths a multiple of 8: the bf16 rows are 16-B aligned with no padding)

@@ -755,6 +755,77 @@ def test_bf16_big_tile_gemm_equals_tiled(epi, monkeypatch):
         assert np.abs(got - want).max() / np.abs(want).max() < 2e-5, (M, N, K, dual)
 
 
+def test_bf16_gemm_epilogue_tails(monkeypatch):
+    """The arms of the 32 x 32 tile epilogue (three copies: tiled, streaming, small-M) and
+    of the 256 x 256 kernel's 8-column one that the tests above, with ldc = ldh = N, never
+    reach: the scalar path (ldc = N + 1), vector runs that stop short of a padded ldc
+    (N rounded up to 8 > N), and DTANH whose ldh forbids the vector path while ldc allows
+    it (ldh = N + 1) or allows it too (ldh = ldc).  Shapes: the smallest with two row
+    tiles and a partial column tile per kernel.  (a) every kernel equals the tiled one bit
+    for bit on the M x N block; (b) the tiled result is within 2e-5 (f32) / 8e-3 (bf16
+    output) of the float64 product of the bf16 operands; (c) the padding columns
+    N <= c < ldc keep their sentinel.  The streaming shapes' A and Bt carry lda = ldb =
+    the kernel's K plan (384 / 512): its A fragments of all but the last k-step are read
+    without a bound, so a row shorter than the plan less 16 is read past its end."""
+    import ctypes
+
+    from modular_rl_amd import _lib
+    from modular_rl_amd._lib import call, stream
+    rng = np.random.default_rng(31)
+    EPI = {"store": _lib.GEMM_STORE, "tanh": _lib.GEMM_TANH, "dtanh": _lib.GEMM_DTANH}
+    ENV = ("MRL_GEMM_BIG_MIN_M", "MRL_GEMM_STREAM_MIN_M", "MRL_GEMM_SMALL_MAX_M")
+    TILED = ("0", "0", "0")
+    # kernel, its (big, stream, small) thresholds (None: unset), M, N, K, lda = ldb, has DTANH
+    for (kernel, env, M, N, K, ldk, dt) in [("tiled", TILED, 130, 70, 40, 40, True),
+                                            ("small", ("0", "0", "8192"), 70, 70, 40, 40, False),
+                                            ("stream", ("0", "1", "0"), 300, 70, 264, 384, True),
+                                            ("stream", ("0", "1", "0"), 300, 70, 392, 512, True),
+                                            ("big", ("1", "0", None), 300, 140, 128, 128, True)]:
+        A, W = rng.standard_normal((M, K)), rng.standard_normal((K, N)) * 0.05
+        bias = rng.standard_normal(N).astype(np.float32)
+        H = np.tanh(rng.standard_normal((M, N)))
+        dA, db = _bf16_dev(A, ldk), _dev(bias)
+        Bt = torch.zeros(N * ldk, dtype=torch.int16, device="cuda")
+        dw = _dev(W.astype(np.float32))
+        call("mrl_pack_w_bf16", ctypes.c_void_p(dw.data_ptr()), K, N, 1, ctypes.c_void_p(Bt.data_ptr()), ldk, stream())
+        pre = bfr(A) @ bfr(W) + bias.astype(np.float64)
+        hb = bfr(H)
+        want = {"store": pre, "tanh": np.tanh(pre), "dtanh": pre * (1.0 - hb * hb)}
+        for ldc in (N + 1, (N + 7) // 8 * 8):
+            for epi, ldh in [("store", N), ("tanh", N)] + ([("dtanh", N + 1), ("dtanh", ldc)] if dt else []):
+                dH = _bf16_dev(H, ldh)
+                for out_bf in (0, 1):
+                    outs = []
+                    for e in (TILED, env) if kernel != "tiled" else (TILED,):
+                        for name, val in zip(ENV, e):
+                            if val is None:
+                                monkeypatch.delenv(name, raising=False)
+                            else:
+                                monkeypatch.setenv(name, val)
+                        C = torch.full((M * ldc,), -7, dtype=torch.int16, device="cuda") if out_bf else \
+                            torch.full((M * ldc,), float("nan"), dtype=torch.float32, device="cuda")
+                        g = _lib.GemmBf16Desc(m=M, n=N, k=K, a=ctypes.c_void_p(dA.data_ptr()), lda=ldk,
+                                              bt=ctypes.c_void_p(Bt.data_ptr()), ldb=ldk,
+                                              c=ctypes.c_void_p(C.data_ptr()), ldc=ldc, c_bf16=out_bf, epilogue=EPI[epi],
+                                              bias=ctypes.c_void_p(db.data_ptr()), h=ctypes.c_void_p(dH.data_ptr()),
+                                              ldh=ldh)
+                        call("mrl_gemm_bf16", ctypes.byref(g), None, stream())
+                        torch.cuda.synchronize()
+                        outs.append(C.view(M, ldc))
+                    case = (kernel, M, N, K, ldc, epi, ldh, out_bf)
+                    for C in outs:  # (c)
+                        pad = C[:, N:]
+                        assert bool((pad == -7).all() if out_bf else torch.isnan(pad).all()), case
+                    if kernel != "tiled":  # (a)
+                        bits = torch.int16 if out_bf else torch.int32
+                        diff = (outs[0][:, :N].contiguous().view(bits) != outs[1][:, :N].contiguous().view(bits))
+                        assert diff.sum().item() == 0, case + (diff.sum().item(),)
+                    got = _bf16_host(outs[0], M, ldc, N) if out_bf else outs[0][:, :N].cpu().numpy().astype(np.float64)
+                    err = np.abs(got - want[epi]).max() / np.abs(want[epi]).max()  # (b)
+                    print(case, "tiled vs float64", err)
+                    assert err < (8e-3 if out_bf else 2e-5), case + (err,)
+
+
 def test_bf16_lds_limited_gemms_equal_default(monkeypatch):
     """The LDS-capped dispatch (desc.lds_limit > 0: the VF fit's GEMMs while they share CUs
     with the Humanoid rollout) takes only the non-persistent 128-row tiled kernels -- BK 64

@@ -1,6 +1,6 @@
 """Headroom probe: the vendor GEMM (torch.matmul -> hipBLASLt / rocBLAS) on the C5 layered
 shapes (1,048,576 x 512 x 512 NN / NT / TN, bf16 and f32), against which this repo's
-hand-written GEMMs (gemm.hip, gemm_bf16.hip) are compared.  Measurement only: the library
+hand-written GEMMs (gemm.hip, gemm_bf16*.hip) are compared.  Measurement only: the library
 is not on the product path."""
 import torch
 
