@@ -385,6 +385,9 @@ int mrl_probtype_rows(int32_t head, int32_t k, int64_t n, const float* prob, con
  * GAE + discounted return over time-major [T, E] rows (core.py:63-75 with
  * misc_utils.py:9-27 discount): flags bit0 = episode ends at this row, bit1 = the
  * env terminated (bootstrap 0) else bootstrap with the row's own baseline (core.py:73).
+ * bit1 counts only on a row that has bit0.  The final row T - 1 always ends its
+ * episode: without bit0 it is a truncation (bit0 set, its bit1 as given), the horizon cut
+ * of a reference path.  (mrl_episode_stats instead drops a run the batch leaves open.)
  * moments (fp64 [3]) <- (sum adv, sum adv^2, count)  (for core.py:100-105).
  * workspace: mrl_gae_workspace_bytes(T, E) bytes, ZEROED before its first mrl_gae and
  * not written by anything else between calls (it holds a completion counter that each

@@ -443,8 +443,10 @@ int mrl_gae(const float* rew, const float* vpred, const uint8_t* flags, int64_t 
   double* part = reinterpret_cast<double*>(workspace);
   hipStream_t s = (hipStream_t)stream;
   const int L = chunk_len(T, GAE_NC, GAE_LMAX);
-  // MRL_GAE_GENERAL=1 (tests / A-B probes): the general kernel for every shape
-  static const bool general_only = getenv("MRL_GAE_GENERAL") && getenv("MRL_GAE_GENERAL")[0] == '1';
+  // MRL_GAE_GENERAL=1 (tests / A-B probes): the general kernel for every shape; read at
+  // every call (the tests flip it between calls)
+  const char* general_env = getenv("MRL_GAE_GENERAL");
+  const bool general_only = general_env && general_env[0] == '1';
   if (!general_only && T == (int64_t)GAE_NC * L && E % GAE_EB == 0 && T * E * 4 < ((int64_t)1 << 31)) {
     // exact fit: one pass, the moments finished by the last block (gae_full_kernel)
     uint32_t* ticket = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) + gae_ticket_offset(E));

@@ -118,12 +118,13 @@ def sum_rows_pairwise(slab):
 def moments_ref(a, b=None, shift=0.0):
     """mrl_moments / mrl_moments_centered: (sum d, sum d^2, n) of d = a - b - shift, EXACT.
     a, b float32 multiples of 2^-10 below 2^23 (the generators above; checked): a - b is
-    then exact in fp64.  d = (a - b) - shift is held as the unevaluated
+    then exact in fp64; with b None any float32 a is (no difference is formed), so nothing
+    is asked of it.  d = (a - b) - shift is held as the unevaluated
     pair hi + lo (TwoSum), d^2 = hi^2 + 2 hi lo + lo^2 with every product split exactly
     (Dekker), and math.fsum adds all the pieces with one rounding.
     Returns (s1, s2, sum |d|, sum d^2)."""
     d0 = np.asarray(a, dtype=np.float64) - (0.0 if b is None else np.asarray(b, dtype=np.float64))
-    assert np.all(np.rint(d0 * 1024.0) == d0 * 1024.0) and np.all(np.abs(d0) < 2.0 ** 24)
+    assert b is None or (np.all(np.rint(d0 * 1024.0) == d0 * 1024.0) and np.all(np.abs(d0) < 2.0 ** 24))
     hi, lo = F.two_sum(d0, np.full_like(d0, -float(shift)))
     s1 = math.fsum(np.concatenate([hi, lo]))
     pieces = []
