@@ -421,8 +421,7 @@ __global__ __launch_bounds__(256) void head_rows_kernel(RowsArgs a, const float*
   }
   double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0;
   if constexpr (EPI == MRL_EPI_PPOSGD) {
-    // one minibatch (n <= 256) in one block: block-reduced kl sets the penalty slope
-    __shared__ double red[4];
+    // one minibatch (n <= MRL_PPO_BLOCK_ROWS) in one block, one row per thread (pposgd_row)
     const int64_t row = threadIdx.x;
     const bool valid = row < a.n;
     float z[MA], dz[MA];
@@ -431,15 +430,7 @@ __global__ __launch_bounds__(256) void head_rows_kernel(RowsArgs a, const float*
       z[j] = (valid && j < A) ? zr[row * A + j] : 0.f;
       dz[j] = 0.f;
     }
-    if (valid) row_epilogue<MRL_EPI_LOSSES, MA>(a, row, z, dz, ls, sd, dls, acc0, acc1, acc2);
-    const double klw = wave_sum(acc1);
-    if (lane == 0) red[wave] = klw;
-    __syncthreads();
-    const double kl = ((red[0] + red[1]) + (red[2] + red[3])) * a.inv_ng;
-    RowsArgs b = a;
-    b.kl_coeff = a.kl_coeff + (kl > a.kl_cutoff ? (float)(2.0 * a.cutoff_coeff * (kl - a.kl_cutoff)) : 0.f);
-    double d0 = 0.0, d1 = 0.0, d2 = 0.0;
-    if (valid) row_epilogue<MRL_EPI_PPOGRAD, MA>(b, row, z, dz, ls, sd, dls, d0, d1, d2);
+    pposgd_row<MA>(a, row, valid, z, dz, ls, sd, dls, acc0, acc1, acc2);
   } else {
     for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < a.n; row += (int64_t)gridDim.x * 256) {
       float z[MA], dz[MA];

@@ -218,7 +218,9 @@ __global__ __launch_bounds__(ROWS_BLOCK_B, (rows_b_occ<EPI_K, SH>())) void mlp_r
     dls[j] = (a.dlogstd != nullptr && j < A) ? a.dlogstd[j] : 0.f;
   }
   double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0;
-  const int64_t ntiles = (a.n + 31) / 32;
+  // PPOSGD (one block, n <= MRL_PPO_BLOCK_ROWS): every wave takes its tile exactly once, past
+  // the end with all rows invalid, so the whole block meets in pposgd_row's reduction
+  const int64_t ntiles = EPI == MRL_EPI_PPOSGD ? MRL_PPO_BLOCK_ROWS / 32 : (a.n + 31) / 32;
   for (int64_t tile = (int64_t)blockIdx.x * 4 + wave; tile < ntiles; tile += (int64_t)gridDim.x * 4) {
     const int64_t row = tile * 32 + (lane & 31);
     const bool valid = row < a.n;
@@ -244,16 +246,7 @@ __global__ __launch_bounds__(ROWS_BLOCK_B, (rows_b_occ<EPI_K, SH>())) void mlp_r
       for (int o = 0; o < MAX_OUT; ++o) dz[o] = 0.f;
     }
     if constexpr (EPI == MRL_EPI_PPOSGD) {
-      __shared__ double red[4];
-      if (valid && h == 0) row_epilogue<MRL_EPI_LOSSES, MAX_OUT>(a, row, z, dz, ls, sd, dls, acc0, acc1, acc2);
-      const double klw = wave_sum(acc1);
-      if (lane == 0) red[wave] = klw;
-      __syncthreads();
-      const double kl = ((red[0] + red[1]) + (red[2] + red[3])) * a.inv_ng;
-      RowsArgs c = a;
-      c.kl_coeff = a.kl_coeff + (kl > a.kl_cutoff ? (float)(2.0 * a.cutoff_coeff * (kl - a.kl_cutoff)) : 0.f);
-      double d0 = 0.0, d1 = 0.0, d2 = 0.0;
-      if (valid && h == 0) row_epilogue<MRL_EPI_PPOGRAD, MAX_OUT>(c, row, z, dz, ls, sd, dls, d0, d1, d2);
+      pposgd_row<MAX_OUT>(a, row, valid && h == 0, z, dz, ls, sd, dls, acc0, acc1, acc2);
       continue;
     } else {
       if constexpr (EPI == MRL_EPI_PROB)

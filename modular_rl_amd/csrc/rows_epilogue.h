@@ -4,6 +4,7 @@
 // KL / entropy partial sums, the head-gradient row, or the VF squared error.
 #pragma once
 #include "../../include/mrl_hip.h"
+#include "mlp_device.h"
 #include "mlp_layout.h"
 
 namespace mrl {
@@ -215,6 +216,29 @@ __device__ __forceinline__ void row_epilogue(const RowsArgs& a, int64_t row, con
       for (int j = 0; j < A; ++j) st_head<LDSHEAD>(a.ghead + row * a.gh + j, g[j]);
     }
   }
+}
+
+// EPI_PPOSGD of one row: one minibatch of n <= MRL_PPO_BLOCK_ROWS rows per launch, in ONE
+// block of 4 waves (ppo.py:150-156).  The block-reduced minibatch KL sets the penalty
+// slope, then the row's pensurr head gradient is written; the row's LOSSES terms go to
+// acc0..2.  EVERY thread of the block calls this exactly once, outside any loop whose trip
+// count depends on n -- `valid` false for a thread without a row, which adds 0 to the KL --
+// so all four red[] slots are written and all four waves reach the barrier whatever n is.
+template <int MA>
+__device__ __forceinline__ void pposgd_row(const RowsArgs& a, int64_t row, bool valid, const float (&z)[MA],
+                                           const float (&dz)[MA], const float (&ls)[MA], const float (&sd)[MA],
+                                           const float (&dls)[MA], double& acc0, double& acc1, double& acc2) {
+  __shared__ double red[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (valid) row_epilogue<MRL_EPI_LOSSES, MA>(a, row, z, dz, ls, sd, dls, acc0, acc1, acc2);
+  const double klw = wave_sum(acc1);
+  if (lane == 0) red[wave] = klw;
+  __syncthreads();
+  const double kl = ((red[0] + red[1]) + (red[2] + red[3])) * a.inv_ng;
+  RowsArgs b = a;
+  b.kl_coeff = a.kl_coeff + (kl > a.kl_cutoff ? (float)(2.0 * a.cutoff_coeff * (kl - a.kl_cutoff)) : 0.f);
+  double d0 = 0.0, d1 = 0.0, d2 = 0.0;
+  if (valid) row_epilogue<MRL_EPI_PPOGRAD, MA>(b, row, z, dz, ls, sd, dls, d0, d1, d2);
 }
 
 }  // namespace mrl
