@@ -430,6 +430,9 @@ int64_t mrl_episode_stats_workspace_bytes(int64_t E);
 #define MRL_ENV_PENDULUM 4     /* Pendulum-v0 equations (gym): obs 3, one torque in [-2, 2], TimeLimit 200  */
 #define MRL_ENV_MOUNTAINCAR 5  /* MountainCar-v0 equations (gym): obs 2, k = 3, TimeLimit 200               */
 #define MRL_ENV_ACROBOT 6      /* Acrobot-v1 equations (gym, "book", RK4): obs 6, k = 3, TimeLimit 500      */
+/* 7 is not an env */
+#define MRL_ENV_INVPENDULUM 8        /* InvertedPendulum-v2: cart + pole chain, obs 4, one force in [-3, 3], TimeLimit 1000 */
+#define MRL_ENV_INVDOUBLEPENDULUM 9  /* InvertedDoublePendulum-v2: cart + two poles, obs 11, one force in [-1, 1], TimeLimit 1000 */
 
 typedef struct {
   int32_t env_id;          /* MRL_ENV_*                                          */
@@ -536,8 +539,9 @@ int mrl_rollout_finish(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, voi
  * they read env_id, n_envs, timestep_limit (<= 0: none), env_offset and seed; from the
  * bufs env_state and env_int only -- a Collector's envs and a stand-alone handle are the
  * same object.  Observations are the raw fp64 rows; mrl_obfilter_update_apply is the
- * ZFilter over them.  Every MRL_ENV_* id is served: CartPole, Hopper, Pendulum, MountainCar
- * and Acrobot by a thread per env, Humanoid by a wave per env. */
+ * ZFilter over them.  Every MRL_ENV_* id is served: CartPole, Hopper, Pendulum, MountainCar,
+ * Acrobot, InvertedPendulum and InvertedDoublePendulum by a thread per env, Humanoid by a wave
+ * per env. */
 typedef struct {
   const void* act;       /* step: [E] int32 (discrete) | [E, act_dim] float            */
   const uint8_t* mask;   /* reset: NULL = every env, else [E], non-zero = reset        */
@@ -598,7 +602,8 @@ typedef struct {
  * mrl_obfilter_update_apply(update = 0, clip = 5) gives; NULL or n_obs < 2: the raw
  * observation, clipped only.  From the desc: env_id, n_envs, timestep_limit, env_offset, seed;
  * from the bufs: env_state, env_int.  Every env but Humanoid (CartPole, Hopper, Pendulum,
- * MountainCar, Acrobot) with its 64-64 policy net; anything else is MRL_E_UNSUPPORTED. */
+ * MountainCar, Acrobot, InvertedPendulum, InvertedDoublePendulum) with its 64-64 policy net;
+ * anything else is MRL_E_UNSUPPORTED. */
 int mrl_pop_rollout(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, const mrl_mlp_desc* pol,
                     const float* thetas, int64_t ld_theta, const double* filter_state,
                     const mrl_pop_io* io, void* stream);

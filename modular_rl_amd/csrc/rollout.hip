@@ -749,9 +749,11 @@ __device__ inline bool gather_granules(const Granules& gr, RecRoundT<R>& rr, int
   }
 }
 
-// initial state of env e's episode number epc (reset_env's Philox draw, domain 1)
+// initial state of env e's episode number epc (reset_env's Philox draw, domain 1).  Always
+// inlined: as a call (the double pendulum's Box-Muller reset is past the inliner's size limit)
+// the state it fills would live in scratch.
 template <int ENV>
-__device__ inline void episode_start_state(const RollArgs& a, int e, uint32_t epc, double* s) {
+__device__ __attribute__((always_inline)) inline void episode_start_state(const RollArgs& a, int e, uint32_t epc, double* s) {
   const uint32_t gid = (uint32_t)(a.d.env_offset + e);
   double u[EnvC<ENV>::NU];
 #pragma unroll

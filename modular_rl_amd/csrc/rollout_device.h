@@ -9,6 +9,7 @@
 
 #include "../../include/mrl_hip.h"
 #include "envs.h"
+#include "envs_chains.h"
 #include "envs_classic.h"
 #include "mlp_device.h"
 
@@ -161,6 +162,50 @@ struct EnvC<MRL_ENV_ACROBOT> {
   }
 };
 
+// the cart-and-pole chains (envs_chains.h): a thread steps an env whole, like Pendulum
+template <>
+struct EnvC<MRL_ENV_INVPENDULUM> {
+  static constexpr int NS = IP_NS, OBS = IP_OBS, ACT = IP_ACT, DISCRETE = 0, MAX_STEPS = 1000, NU = IP_NU,
+                       OBS_SLOTS = 0;
+  __device__ static void reset(const double* u, double* s) { invpendulum_reset(u, s); }
+  __device__ static void obs(const double* s, double* o) { invpendulum_obs(s, o); }
+  __device__ static void step_disc(double*, int, double&, bool&) {}
+  __device__ static void step_cont(double* s, const float* a, double& rew, bool& done) {
+    invpendulum_step(s, a, rew, done);
+  }
+  __device__ static void step_cont_quad(double* s, const float* a, double& rew, bool& done, int, const double*) {
+    invpendulum_step(s, a, rew, done);
+  }
+  template <class Out>
+  __device__ static void obs_out(const double* s, Out out) {
+    double o[OBS];
+    invpendulum_obs(s, o);
+#pragma unroll
+    for (int k = 0; k < OBS; ++k) out(k, o[k]);
+  }
+};
+template <>
+struct EnvC<MRL_ENV_INVDOUBLEPENDULUM> {
+  static constexpr int NS = DP_NS, OBS = DP_OBS, ACT = DP_ACT, DISCRETE = 0, MAX_STEPS = 1000, NU = DP_NU,
+                       OBS_SLOTS = 0;
+  __device__ static void reset(const double* u, double* s) { invdoublependulum_reset(u, s); }
+  __device__ static void obs(const double* s, double* o) { invdoublependulum_obs(s, o); }
+  __device__ static void step_disc(double*, int, double&, bool&) {}
+  __device__ static void step_cont(double* s, const float* a, double& rew, bool& done) {
+    invdoublependulum_step(s, a, rew, done);
+  }
+  __device__ static void step_cont_quad(double* s, const float* a, double& rew, bool& done, int, const double*) {
+    invdoublependulum_step(s, a, rew, done);
+  }
+  template <class Out>
+  __device__ static void obs_out(const double* s, Out out) {
+    double o[OBS];
+    invdoublependulum_obs(s, o);
+#pragma unroll
+    for (int k = 0; k < OBS; ++k) out(k, o[k]);
+  }
+};
+
 struct EnvInfo {
   int ns, obs, act, discrete, max_steps;
 };
@@ -170,12 +215,15 @@ __host__ __device__ inline EnvInfo env_info(int id) {
   if (id == MRL_ENV_PENDULUM) return EnvInfo{PD_NS, PD_OBS, PD_ACT, 0, 200};
   if (id == MRL_ENV_MOUNTAINCAR) return EnvInfo{MC_NS, MC_OBS, 3, 1, 200};
   if (id == MRL_ENV_ACROBOT) return EnvInfo{AC_NS, AC_OBS, 3, 1, 500};
+  if (id == MRL_ENV_INVPENDULUM) return EnvInfo{IP_NS, IP_OBS, IP_ACT, 0, 1000};
+  if (id == MRL_ENV_INVDOUBLEPENDULUM) return EnvInfo{DP_NS, DP_OBS, DP_ACT, 0, 1000};
   return EnvInfo{HP_NS, HP_OBS, HP_ACT, 0, 1000};
 }
-// the ids the entry points take (MRL_ENV_*; 3 is not one)
+// the ids the entry points take (MRL_ENV_*; 3 and 7 are not)
 __host__ __device__ inline bool env_known(int id) {
   return id == MRL_ENV_CARTPOLE || id == MRL_ENV_HOPPER || id == MRL_ENV_HUMANOID || id == MRL_ENV_PENDULUM ||
-         id == MRL_ENV_MOUNTAINCAR || id == MRL_ENV_ACROBOT;
+         id == MRL_ENV_MOUNTAINCAR || id == MRL_ENV_ACROBOT || id == MRL_ENV_INVPENDULUM ||
+         id == MRL_ENV_INVDOUBLEPENDULUM;
 }
 __host__ __device__ inline int filt_doubles(int obs) { return 2 + 2 * (obs + 1); }
 

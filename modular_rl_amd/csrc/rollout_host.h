@@ -64,6 +64,10 @@ inline int check_fused_run(const mrl_rollout_desc* d, const mrl_mlp_desc* pol, c
     else if ((id) == MRL_ENV_MOUNTAINCAR)                                                         \
       hipLaunchKernelGGL(KERNEL<MRL_ENV_MOUNTAINCAR>, __VA_ARGS__);                               \
     else if ((id) == MRL_ENV_ACROBOT) hipLaunchKernelGGL(KERNEL<MRL_ENV_ACROBOT>, __VA_ARGS__);    \
+    else if ((id) == MRL_ENV_INVPENDULUM)                                                         \
+      hipLaunchKernelGGL(KERNEL<MRL_ENV_INVPENDULUM>, __VA_ARGS__);                               \
+    else if ((id) == MRL_ENV_INVDOUBLEPENDULUM)                                                   \
+      hipLaunchKernelGGL(KERNEL<MRL_ENV_INVDOUBLEPENDULUM>, __VA_ARGS__);                         \
     else hipLaunchKernelGGL(KERNEL<MRL_ENV_HUMANOID>, __VA_ARGS__);                               \
   } while (0)
 
@@ -75,6 +79,8 @@ inline void dispatch_thread_env(int id, F&& f) {
   else if (id == MRL_ENV_PENDULUM) f(std::integral_constant<int, MRL_ENV_PENDULUM>{});
   else if (id == MRL_ENV_MOUNTAINCAR) f(std::integral_constant<int, MRL_ENV_MOUNTAINCAR>{});
   else if (id == MRL_ENV_ACROBOT) f(std::integral_constant<int, MRL_ENV_ACROBOT>{});
+  else if (id == MRL_ENV_INVPENDULUM) f(std::integral_constant<int, MRL_ENV_INVPENDULUM>{});
+  else if (id == MRL_ENV_INVDOUBLEPENDULUM) f(std::integral_constant<int, MRL_ENV_INVDOUBLEPENDULUM>{});
   else f(std::integral_constant<int, MRL_ENV_HOPPER>{});
 }
 #define MRL_DISPATCH_THREAD_ENV(id, KERNEL, ...) \

@@ -1,6 +1,6 @@
 """Env registry for the device env steppers (replaces ``gym.envs.make``, run_pg.py:85).
 
-The dynamics live in ``csrc/envs.h`` / ``csrc/envs_classic.h`` / ``csrc/humanoid.h`` and run inside the rollout
+The dynamics live in ``csrc/envs.h`` / ``csrc/envs_classic.h`` / ``csrc/envs_chains.h`` / ``csrc/humanoid.h`` and run inside the rollout
 kernels; this module describes them with gym-compatible spaces / spec so that
 ``TrpoAgent(env.observation_space, env.action_space, cfg)`` and
 ``env.spec.max_episode_steps`` (run_pg.py:103-108) work unchanged, and ``VecEnv`` steps
@@ -14,6 +14,10 @@ them with the caller's own actions (``mrl_env_reset`` / ``mrl_env_step``).
 * ``Pendulum-v0``, ``MountainCar-v0``, ``Acrobot-v1`` -- gym's classic-control equations
   (``csrc/envs_classic.h``): a 1-d torque in [-2, 2] (TimeLimit 200, never done by itself),
   three discrete actions (TimeLimit 200) and three discrete torques (TimeLimit 500).
+* ``InvertedPendulum-v2``, ``InvertedDoublePendulum-v2`` -- gym's cart-and-pole XML models as
+  2- / 3-dof rigid-body chains (``csrc/envs_chains.h``: RK4, penalty joint limits): obs 4 / 11,
+  one slider force in [-3, 3] / [-1, 1], TimeLimit 1000; done at |angle| > 0.2 / tip height <= 1.
+  MuJoCo is not available, so their dynamics are a stand-in like Hopper's.
 """
 import ctypes
 
@@ -57,6 +61,10 @@ REGISTRY = {
                         act_high=2.0),
     "MountainCar-v0": dict(kind=_lib.ENV_MOUNTAINCAR, obs=2, act=3, discrete=True, max_steps=200, obs_high=np.inf),
     "Acrobot-v1": dict(kind=_lib.ENV_ACROBOT, obs=6, act=3, discrete=True, max_steps=500, obs_high=np.inf),
+    "InvertedPendulum-v2": dict(kind=_lib.ENV_INVPENDULUM, obs=4, act=1, discrete=False, max_steps=1000,
+                                obs_high=np.inf, act_high=3.0),
+    "InvertedDoublePendulum-v2": dict(kind=_lib.ENV_INVDOUBLEPENDULUM, obs=11, act=1, discrete=False, max_steps=1000,
+                                      obs_high=np.inf, act_high=1.0),
 }
 
 
