@@ -603,10 +603,31 @@ typedef struct {
  * observation, clipped only.  From the desc: env_id, n_envs, timestep_limit, env_offset, seed;
  * from the bufs: env_state, env_int.  Every env but Humanoid (CartPole, Hopper, Pendulum,
  * MountainCar, Acrobot, InvertedPendulum, InvertedDoublePendulum) with its 64-64 policy net;
- * anything else is MRL_E_UNSUPPORTED. */
+ * anything else is MRL_E_UNSUPPORTED here -- smaller nets (the reference's CEM battery runs
+ * hid_sizes 10,5) go through mrl_pop_rollout_mlp below. */
 int mrl_pop_rollout(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, const mrl_mlp_desc* pol,
                     const float* thetas, int64_t ld_theta, const double* filter_state,
                     const mrl_pop_io* io, void* stream);
+
+/* The same rollout for a small net: the tanh MLP obs -> hid_sizes[0] -> ... -> act of env_id
+ * with the env's head (softmax | Gauss), n_hid hidden layers (0: the linear policy x W + b).
+ * A block keeps the forward parameters of its 64 candidates in LDS for the whole episode, so
+ * the shape must fit: mrl_pop_rollout_mlp_fits, 1 or 0 (Humanoid, n_hid > 3, a width outside
+ * [1, 64] and a population tile beyond one block's LDS are 0), negative on bad arguments.
+ * mrl_pop_mlp_num_params: the length of one theta in flat Keras order (W0, b0, ..., logstd
+ * included for a Gauss head), negative on bad arguments (unknown env, n_hid < 0, null hid_sizes
+ * with n_hid > 0, a width < 1).
+ * mrl_pop_rollout_mlp: everything mrl_pop_rollout documents -- reset stream and counter, frozen
+ * filter, deterministic action, end of episode, ld_theta == 0, the outputs and the trace,
+ * env_state / env_int -- with the same arithmetic: per unit an fmaf chain over the inputs in
+ * ascending order from 0, plus the bias, tanhf on hidden layers.  A shape that does not fit is
+ * MRL_E_UNSUPPORTED. */
+int64_t mrl_pop_mlp_num_params(int32_t env_id, const int32_t* hid_sizes, int32_t n_hid);
+int32_t mrl_pop_rollout_mlp_fits(int32_t env_id, const int32_t* hid_sizes, int32_t n_hid);
+int mrl_pop_rollout_mlp(const mrl_rollout_desc* d, const mrl_rollout_bufs* b,
+                        const int32_t* hid_sizes, int32_t n_hid,
+                        const float* thetas, int64_t ld_theta, const double* filter_state,
+                        const mrl_pop_io* io, void* stream);
 
 /* thetas[i, p] = (float)(mean[p] + sample_std[p] * z(i, p)), product and sum in fp64 (cem.py:42);
  * z: Box-Muller (as the rollout's sampling noise) of Philox (seed, domain 2, gid i, word

@@ -178,6 +178,9 @@ SIGNATURES = {
     "mrl_obfilter_workspace_bytes": (i64, [i64, i32]),
     "mrl_obfilter_update_apply": (i32, [vp, i32, vp, i64, i32, f64, vp, vp, vp]),
     "mrl_pop_rollout": (i32, [vp, vp, vp, vp, i64, vp, vp, vp]),
+    "mrl_pop_mlp_num_params": (i64, [i32, vp, i32]),
+    "mrl_pop_rollout_mlp_fits": (i32, [i32, vp, i32]),
+    "mrl_pop_rollout_mlp": (i32, [vp, vp, vp, i32, vp, i64, vp, vp, vp]),
     "mrl_cem_sample": (i32, [vp, vp, i64, i64, ctypes.c_uint64, ctypes.c_uint64, vp, i64, vp]),
     "mrl_cem_refit_workspace_bytes": (ctypes.c_size_t, [i64, i64]),
     "mrl_cem_refit": (i32, [vp, i64, i64, i64, vp, i32, vp, vp, vp, vp, vp]),

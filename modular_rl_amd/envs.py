@@ -213,7 +213,7 @@ class PopulationRollout:
     policy (the Gauss head's mean / the arg-max logit).
 
     ``pop(thetas, filter_state=None, trace_steps=0)`` takes float32 ``[n, P]`` device rows
-    (flat Keras-order theta of the env's 64-64 policy net) and returns a dict of tensors the
+    (flat Keras-order theta of the env's policy net, ``pop.P`` floats) and returns a dict of tensors the
     object owns: ``ret`` (float64 sum of raw rewards), ``len``, ``flags`` (bit 1:
     terminated), ``stat`` (``[n, 1 + 2 obs_dim]`` Welford count / mean / M2 of the raw
     observations each policy was fed) and, with ``trace_steps > 0``, ``trace_obs`` /
@@ -224,9 +224,16 @@ class PopulationRollout:
 
     Every call starts a new episode in every env: the reset stream is the ``VecEnv``'s
     (seed, env, episodes started), so a ``VecEnv`` with the same seed replays a traced call.
+
+    ``hid_sizes``: the hidden widths of the tanh policy net.  The default ``(64, 64)`` is the
+    env's 64-64 net (``mrl_pop_rollout``, theta streamed from memory every step).  Any other
+    shape -- ``(10, 5)`` of the reference's CEM battery, ``()`` for the linear policy -- runs on
+    ``mrl_pop_rollout_mlp``, which keeps a block's 64 candidates in LDS for the whole episode:
+    up to three hidden layers of 1 .. 64 units whose population tile fits one block's LDS
+    (``mrl_pop_rollout_mlp_fits``); a shape that does not raises ``MrlError`` here.
     """
 
-    def __init__(self, env_id, n, seed=0, timestep_limit=None, env_offset=0, device="cuda"):
+    def __init__(self, env_id, n, seed=0, timestep_limit=None, env_offset=0, device="cuda", hid_sizes=(64, 64)):
         env = env_id if isinstance(env_id, DeviceEnv) else DeviceEnv(env_id)
         if int(n) <= 0:
             raise ValueError(f"n must be positive, got {n}")
@@ -237,9 +244,23 @@ class PopulationRollout:
         self.limit = min(limit, env.spec.max_episode_steps)
         self.desc = _lib.RolloutDesc(env.kind, self.N, 1, self.limit, 0, int(env_offset),
                                      int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.COMPUTE_F32, 0)
-        head = _lib.HEAD_SOFTMAX if env.discrete else _lib.HEAD_GAUSS
-        self.pol = _lib.MlpDesc(env.obs_dim, env.act_dim, head, 64, 2)
-        self.P = int(lib.mrl_mlp_num_params(ctypes.byref(self.pol)))
+        self.hid_sizes = tuple(int(h) for h in hid_sizes)
+        if self.hid_sizes == (64, 64):
+            head = _lib.HEAD_SOFTMAX if env.discrete else _lib.HEAD_GAUSS
+            self.pol = _lib.MlpDesc(env.obs_dim, env.act_dim, head, 64, 2)
+            self.P = int(lib.mrl_mlp_num_params(ctypes.byref(self.pol)))
+        else:
+            self.pol = None
+            self._hid = (ctypes.c_int32 * max(len(self.hid_sizes), 1))(*self.hid_sizes)
+            fits = int(lib.mrl_pop_rollout_mlp_fits(env.kind, self._hid, len(self.hid_sizes)))
+            _lib.check(min(fits, 0), "mrl_pop_rollout_mlp_fits")
+            if fits != 1:
+                raise _lib.MrlError(f"PopulationRollout: hid_sizes={list(self.hid_sizes)} on {env.spec.id} is neither "
+                                    "the 64-64 net nor a net mrl_pop_rollout_mlp takes (every env but Humanoid, at "
+                                    "most 3 hidden layers of 1..64 units, 64 candidates' parameters within one "
+                                    "block's LDS)")
+            self.P = int(lib.mrl_pop_mlp_num_params(env.kind, self._hid, len(self.hid_sizes)))
+            _lib.check(min(self.P, 0), "mrl_pop_mlp_num_params")
         N, O = self.N, env.obs_dim
         f64 = dict(dtype=torch.float64, device=self.dev)
         self.env_state = torch.zeros(int(lib.mrl_env_state_doubles(env.kind)) * N, **f64)
@@ -278,8 +299,12 @@ class PopulationRollout:
             tobs, tact, trew = self._trace_bufs(int(trace_steps))
             io.trace_steps, io.trace_obs, io.trace_act, io.trace_rew = int(trace_steps), p(tobs), p(tact), p(trew)
             out.update(trace_obs=tobs, trace_act=tact, trace_rew=trew)
-        _lib.call("mrl_pop_rollout", ctypes.byref(self.desc), ctypes.byref(self._bufs), ctypes.byref(self.pol),
-                  p(thetas), ld, p(fs), ctypes.byref(io), _lib.stream())
+        if self.pol is not None:
+            _lib.call("mrl_pop_rollout", ctypes.byref(self.desc), ctypes.byref(self._bufs), ctypes.byref(self.pol),
+                      p(thetas), ld, p(fs), ctypes.byref(io), _lib.stream())
+        else:
+            _lib.call("mrl_pop_rollout_mlp", ctypes.byref(self.desc), ctypes.byref(self._bufs), self._hid,
+                      len(self.hid_sizes), p(thetas), ld, p(fs), ctypes.byref(io), _lib.stream())
         return out
 
     def _theta(self, th, shape):
