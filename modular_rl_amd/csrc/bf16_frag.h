@@ -1,9 +1,10 @@
-// bf16 MFMA fragment helpers shared by the bf16 throughput mode (mlp_bf16.hip) and the
-// split-operand fp32 Fisher product (mlp_split.hip): the packed bf16 image layout, the
-// F-tile <-> fragment conversions and the chained layer products on
+// bf16 MFMA fragment helpers shared by the bf16 throughput mode (mlp_bf16.hip,
+// mlp_bf16_device.h) and the split-operand fp32 Fisher product (mlp_split.hip): the packed
+// bf16 image layout, the F-tile <-> fragment conversions and the chained layer products on
 // v_mfma_f32_32x32x16_bf16.  See mlp_bf16.hip's header for the layouts.
 #pragma once
 #include "mlp_device.h"
+#include "rows_epilogue.h"
 
 namespace mrl {
 
@@ -38,6 +39,13 @@ __host__ __device__ constexpr BDims bf16_dims(int O, int A) {
   b.bt1 = o; o += 2 * 4 * 64 * 4;
   b.total_words = o;
   return b;
+}
+
+// rows_shape (rows_epilogue.h) for the kernels that take the bf16 image's dimensions too
+template <int SH>
+__device__ inline void rows_shape(RowsArgs& a, BDims& b) {
+  rows_shape<SH>(a);
+  if constexpr ((SH & ~SH_TIME) != 0) b = bf16_dims(STATIC_SHAPES[SH & ~SH_TIME].O, STATIC_SHAPES[SH & ~SH_TIME].A);
 }
 
 // the f32 kernels' VALU head helpers read d.hv / d.hb: point them at this image's copies

@@ -103,20 +103,6 @@ __device__ inline void mfma_split(const float* img, int seg, int PS, int f, int 
 // interleaved into the previous phase's MFMA chain)
 #define FVP_SPLIT_FENCE() __builtin_amdgcn_sched_barrier(0)
 
-template <int SH>
-__device__ inline void split_shape(RowsArgs& a, BDims& b) {
-  if constexpr (SH != 0) {
-    constexpr StaticShape S = STATIC_SHAPES[SH];
-    a.d = static_dims(SH);
-    a.A = S.A;
-    a.head = S.head;
-    a.n_obs = S.O;
-    a.gh = S.head == MRL_HEAD_GAUSS ? 2 * S.A : S.A;
-    a.ept = nullptr;
-    b = bf16_dims(S.O, S.A);
-  }
-}
-
 // The JVP of one 32-row tile per call (trpo.py:45-58): the head tangent along the tangent
 // image imt from the cached f32 h1 / h2, then sink(valid, row, z, dz) per row of lane half
 // 0 (the standalone kernel: row_epilogue FVP).  Software pipeline (SQ, round 4: 0.39 of the

@@ -1,6 +1,11 @@
 // bf16 throughput mode of the fused 64-wide MLP kernels (MRL_COMPUTE_BF16): the same
 // passes as the f32 kernels of mlp_rows_vjp.hip (forward + row epilogues, Fisher-product
 // JVP, VJP) on v_mfma_f32_32x32x16_bf16 -- 16x the f32 MFMA rate -- with f32 accumulation.
+// The tile forward / JVP and the activation cache are in mlp_bf16_device.h.  The rows and
+// the VJP kernels share this unit on purpose: the uncached VJP recomputes the forward with
+// the rows kernel's forward_b, and hipcc's inlining of it -- and with it the schedule and
+// register allocation of mlp_vjp_bf16_kernel<false, 0> -- depends on its other callers in
+// the unit (in a unit of its own that kernel's code changed), as in mlp_rows_vjp.hip.
 //
 // Rounding points (bf16 RNE): the weights W0, W1 (and the tangent's dW0, dW1), the
 // layer inputs x, h1, h2 and the backpropagated head rows / layer-2 gradients that
@@ -25,10 +30,7 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include "../../include/mrl_hip.h"
-#include "mlp_device.h"
-#include "rows_epilogue.h"
-#include "bf16_frag.h"
+#include "mlp_bf16_device.h"
 #include "mlp_host.h"
 
 namespace mrl {
@@ -60,121 +62,8 @@ __global__ void mlp_pack_bf16_kernel(MlpDims d, BDims b, const float* __restrict
   image[w] = __uint_as_float(v);
 }
 
-// ---- primal activation cache, bf16: per 32-row tile [layer 2][s 4][lane 64] x 16 B
-// (8 KB per tile): every wave load / store instruction moves 1 KB contiguous.
-constexpr int BCACHE_TILE_WORDS = 2 * 4 * 64 * 4;
-__device__ inline void bcache_store(float* tile, int layer, int lane, const bf16x8* fr) {
-#pragma unroll
-  for (int s = 0; s < 4; ++s) reinterpret_cast<bf16x8*>(tile)[(layer * 4 + s) * 64 + lane] = fr[s];
-}
-__device__ inline void bcache_load(const float* tile, int layer, int lane, bf16x8* fr) {
-#pragma unroll
-  for (int s = 0; s < 4; ++s) fr[s] = reinterpret_cast<const bf16x8*>(tile)[(layer * 4 + s) * 64 + lane];
-}
-
-// head partials from a 32-unit tile of bf16-valued h2 (f32 VALU, the f32 kernels' head)
-// forward: h1 / h2 fragments (bf16) and, with the f32 head, z
-template <class XL>
-__device__ inline void forward_b(const float* img, const MlpDims& d, const BDims& b, const XL& xl, int lane,
-                                 bf16x8* h1b, bf16x8* h2b, float* z) {
-  const int h = lane >> 5;
-  bf16x8 xb[MAX_KS0B];
-#pragma unroll
-  for (int s0 = 0; s0 < MAX_KS0B; ++s0) xb[s0] = s0 < b.KS0B ? x_frag(xl, s0, h) : bf16x8{};
-  f32x16 a1[2];
-  a1[0] = load_bias16(img, b.fb0, 0, h);
-  a1[1] = load_bias16(img, b.fb0, 1, h);
-  layer0_b(img, b, xb, lane, a1);
-  tanh16(a1[0]);
-  tanh16(a1[1]);
-#pragma unroll
-  for (int s = 0; s < 4; ++s) h1b[s] = pack8(a1[s >> 1], s & 1);
-#pragma unroll
-  for (int o = 0; o < MAX_OUT; ++o) z[o] = 0.f;
-#pragma unroll
-  for (int mo = 0; mo < 2; ++mo) {
-    f32x16 a = load_bias16(img, b.fb1, mo, h);
-    chain_b(img, b, mo, h1b, lane, a);
-    __builtin_amdgcn_sched_barrier(0);
-    tanh16(a);
-    h2b[2 * mo] = pack8(a, 0);
-    h2b[2 * mo + 1] = pack8(a, 1);
-    const f32x16 ar = unpack16(h2b, mo);
-    head_partial_mt(img, d, ar, mo, h, z);  // d = head_dims(...)
-    // scheduling fences keep the head's weight reads and the next tile's fragment
-    // prefetch from all being hoisted (the static-shape builds otherwise spill)
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  head_finish(img, d, z);
-}
-
-// JVP to the head from cached bf16 h1 / h2 fragments (need_z: also the primal head)
-template <class XL>
-__device__ inline void jvp_b(const float* img, const float* imt, const MlpDims& d, const BDims& b, const XL& xl,
-                             int lane, const bf16x8* h1b, const bf16x8* h2b, float* z, float* dz, bool need_z) {
-  const int h = lane >> 5;
-  bf16x8 xb[MAX_KS0B];
-#pragma unroll
-  for (int s0 = 0; s0 < MAX_KS0B; ++s0) xb[s0] = s0 < b.KS0B ? x_frag(xl, s0, h) : bf16x8{};
-  f32x16 dh[2];
-  dh[0] = load_bias16(imt, b.fb0, 0, h);
-  dh[1] = load_bias16(imt, b.fb0, 1, h);
-  layer0_b(imt, b, xb, lane, dh);
-#pragma unroll
-  for (int m = 0; m < 2; ++m) {
-    const f32x16 h1 = unpack16(h1b, m);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) dh[m][r] *= dtanh(h1[r]);
-  }
-  bf16x8 dhb[4];
-#pragma unroll
-  for (int s = 0; s < 4; ++s) dhb[s] = pack8(dh[s >> 1], s & 1);
-  float dzt[MAX_OUT];
-#pragma unroll
-  for (int o = 0; o < MAX_OUT; ++o) {
-    if (need_z) z[o] = 0.f;
-    dz[o] = 0.f;
-    dzt[o] = 0.f;
-  }
-#pragma unroll
-  for (int mo = 0; mo < 2; ++mo) {
-    f32x16 da = load_bias16(imt, b.fb1, mo, h);
-    chain_b(img, b, mo, dhb, lane, da);
-    chain_b(imt, b, mo, h1b, lane, da);
-    const f32x16 a = unpack16(h2b, mo);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) da[r] *= dtanh(a[r]);
-    if (need_z) head_partial_mt(img, d, a, mo, h, z);
-    head_partial_mt(img, d, da, mo, h, dz);
-    head_partial_mt(imt, d, a, mo, h, dzt);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  if (need_z) head_finish(img, d, z);
-#pragma unroll
-  for (int o = 0; o < MAX_OUT; ++o) dz[o] += dzt[o];
-  head_finish(imt, d, dz);
-}
-
 constexpr int ROWS_BLOCK_B = 256;
 constexpr int ROWS_MAX_BLOCKS_B = 3072;
-constexpr int EPI_FVP_CACHED_B = 100;
-
-// the kernel arguments with a static shape's dimensions substituted (SH == 0: run time;
-// SH | SH_TIME keeps ep_t for the time-feature column)
-template <int SH>
-__device__ inline void rows_shape_b(RowsArgs& a, BDims& b) {
-  if constexpr ((SH & ~SH_TIME) != 0) {
-    constexpr int B = SH & ~SH_TIME;
-    constexpr StaticShape S = STATIC_SHAPES[B];
-    a.d = static_dims(B);
-    a.A = S.A;
-    a.head = S.head;
-    a.n_obs = (SH & SH_TIME) ? S.O - 1 : S.O;
-    a.gh = S.head == MRL_HEAD_GAUSS ? 2 * S.A : S.A;
-    if constexpr (!(SH & SH_TIME)) a.ept = nullptr;
-    b = bf16_dims(S.O, S.A);
-  }
-}
 
 // waves per SIMD the row kernels are compiled for: 3 (168 VGPRs) for the cached FVP pass
 // of the static shapes -- it waits on memory for half its wave time and a third wave
@@ -185,7 +74,7 @@ __device__ inline void rows_shape_b(RowsArgs& a, BDims& b) {
 // shapes at 4 waves.
 template <int EPI_K, int SH>
 constexpr int rows_b_occ() {
-  return ((SH & ~SH_TIME) != 0 && EPI_K == EPI_FVP_CACHED_B) ? 3 : 2;
+  return ((SH & ~SH_TIME) != 0 && EPI_K == EPI_FVP_CACHED) ? 3 : 2;
 }
 
 template <int EPI_K, int SH>
@@ -193,8 +82,8 @@ __global__ __launch_bounds__(ROWS_BLOCK_B, (rows_b_occ<EPI_K, SH>())) void mlp_r
                                                                        const float* __restrict__ img_g,
                                                                        const float* __restrict__ imt_g,
                                                                        const int32_t* __restrict__ skip) {
-  rows_shape_b<SH>(a, b);
-  constexpr bool CACHED = EPI_K == EPI_FVP_CACHED_B;
+  rows_shape<SH>(a, b);
+  constexpr bool CACHED = EPI_K == EPI_FVP_CACHED;
   constexpr int EPI = CACHED ? MRL_EPI_FVP : EPI_K;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   if (skip != nullptr && *skip != 0) return;
@@ -292,8 +181,6 @@ __device__ inline f32x16 transpose_f(const bf16x8* fr, int mt, const bf16x8* ip)
 }
 
 typedef uint32_t vu4 __attribute__((ext_vector_type(4)));  // a 16-B register quad (asm operands)
-
-constexpr int VJP_MAX_BLOCKS_B = 256;  // one block (4 waves) per CU at one wave per SIMD
 
 // SH != 0: a static shape of mlp_layout.h (plain rows), every dimension a constant
 template <int SH>
@@ -619,6 +506,24 @@ __global__ __launch_bounds__(256, 1) void mlp_vjp_bf16_kernel(VjpArgsB a_in, con
   }
 }
 
+static void launch_vjp_bf16(const mrl_mlp_desc* d, const float* image, const float* x, const int32_t* ep_t, double ts_limit,
+                     const float* ghead, int64_t n, float* slab, const float* act_cache, int64_t blocks,
+                     const int32_t* skip, hipStream_t s) {
+  VjpArgsB a = vjp_args<VjpArgsB>(d, x, ep_t, ts_limit, ghead, n, slab, act_cache);
+  a.b = bf16_dims(d->n_in, d->n_out);
+  const size_t shm = (size_t)a.b.total_words * 4;
+  const dim3 grid(blocks), blk(256);
+  // the benchmark policies and value nets as static shapes (plain rows only: the VF
+  // fit reads its materialised [obs, t / limit] rows; a time feature built from ep_t
+  // takes the generic kernel, which spills at the VF's shape)
+  with_bool(act_cache != nullptr, [&](auto cached) {
+    with_static_shape<SH_POLICY | SH_VALUE>(static_shape_of(d, ep_t != nullptr), [&](auto shape) {
+      hipLaunchKernelGGL((mlp_vjp_bf16_kernel<decltype(cached)::value, decltype(shape)::value>), grid, blk, shm, s, a,
+                         image, skip);
+    });
+  });
+}
+
 }  // namespace mrl
 
 using namespace mrl;
@@ -637,6 +542,7 @@ static int64_t rows_blocks_b(int64_t n, bool fvp = false, int64_t cus = 256) {
   }();
   return grid_blocks(n, env_cap > 0 ? env_cap : scaled_cap(fvp ? ROWS_FVP_BLOCKS_B : ROWS_MAX_BLOCKS_B, cus));
 }
+constexpr int VJP_MAX_BLOCKS_B = 256;  // one block (4 waves) per CU at one wave per SIMD
 static int64_t vjp_blocks_b(int64_t n, int64_t cus = 256) { return grid_blocks(n, scaled_cap(VJP_MAX_BLOCKS_B, cus)); }
 
 extern "C" {
@@ -673,110 +579,21 @@ int mrl_mlp_pack_bf16(const mrl_mlp_desc* d, const float* theta, float* image, i
 int mrl_mlp_rows_bf16(const mrl_mlp_desc* d, int32_t epi, const float* theta, const float* image,
                       const float* tangent, const float* image_t, const mrl_rows_io* io, const int32_t* skip,
                       void* stream) {
-  int rc = check_desc(d);
-  if (rc) return rc;
-  if (!io || !image || !io->x) return fail(E_ARG, "null pointer");
-  if (io->n <= 0) return OK;
-  RowsArgs a{};
-  a.d = mlp_dims(d->n_in, d->n_out, d->head == MRL_HEAD_GAUSS);
-  a.head = d->head;
-  a.n_obs = d->n_in - (io->ep_t ? 1 : 0);
-  a.gh = d->head == MRL_HEAD_GAUSS ? 2 * d->n_out : d->n_out;
-  a.A = d->n_out;
-  a.x = io->x;
-  a.ept = io->ep_t;
-  a.ts_limit = io->timestep_limit;
-  a.n = io->n;
-  a.inv_ng = io->inv_n_global;
-  a.act = io->act;
-  a.adv = io->adv;
-  a.oldprob = io->oldprob;
-  a.target = io->target;
-  a.out = io->out;
-  a.ghead = io->ghead;
-  a.partial = io->partial;
-  a.logstd = (d->head == MRL_HEAD_GAUSS && theta) ? theta + a.d.tls : nullptr;
-  a.dlogstd = (d->head == MRL_HEAD_GAUSS && tangent) ? tangent + a.d.tls : nullptr;
-  a.kl_coeff = (float)io->kl_coeff;
-  a.kl_cutoff = (float)io->kl_cutoff;
-  a.cutoff_coeff = (float)io->cutoff_coeff;
-  a.reverse_kl = io->reverse_kl;
-  a.cache = io->act_cache;
-  a.cache_mode = io->act_cache != nullptr ? io->cache_mode : 0;
-  a.feat = io->feat_out;
-  if (a.feat != nullptr && (epi != MRL_EPI_PROB || io->ep_t == nullptr))
-    return fail(E_ARG, "feat_out is for MRL_EPI_PROB with ep_t (the value prediction)");
-  if (a.cache_mode == MRL_CACHE_READ && epi != MRL_EPI_FVP) return fail(E_ARG, "MRL_CACHE_READ is for MRL_EPI_FVP");
-  if (a.cache_mode == MRL_CACHE_WRITE && (epi == MRL_EPI_FVP || epi == MRL_EPI_PPOSGD))
-    return fail(E_ARG, "MRL_CACHE_WRITE is for the plain forward epilogues");
-  switch (epi) {
-    case MRL_EPI_PROB:
-      if (!io->out) return fail(E_ARG, "EPI_PROB needs out");
-      if (d->head == MRL_HEAD_GAUSS && !theta) return fail(E_ARG, "DiagGauss needs theta (logstd)");
-      break;
-    case MRL_EPI_LOSSES:
-    case MRL_EPI_SURRGRAD:
-    case MRL_EPI_PPOGRAD:
-    case MRL_EPI_PPOSGD:
-      if (d->head == MRL_HEAD_LINEAR) return fail(E_ARG, "policy epilogue on a value net");
-      if (!io->act || !io->adv || !io->oldprob || !io->partial) return fail(E_ARG, "losses need act/adv/oldprob/partial");
-      if (epi != MRL_EPI_LOSSES && !io->ghead) return fail(E_ARG, "gradient epilogues need ghead");
-      if (d->head == MRL_HEAD_GAUSS && !theta) return fail(E_ARG, "DiagGauss needs theta (logstd)");
-      if (epi == MRL_EPI_PPOSGD && io->n > MRL_PPO_BLOCK_ROWS) return fail(E_ARG, "PPOSGD minibatch exceeds one block");
-      break;
-    case MRL_EPI_VFLOSS:
-      if (d->head != MRL_HEAD_LINEAR || !io->target || !io->ghead || !io->partial)
-        return fail(E_ARG, "VFLOSS needs a linear head, target, ghead, partial");
-      break;
-    case MRL_EPI_FVP:
-      if (!tangent || !image_t || !io->ghead) return fail(E_ARG, "FVP needs tangent, image_t, ghead");
-      if (d->head == MRL_HEAD_GAUSS && !theta) return fail(E_ARG, "DiagGauss needs theta (logstd)");
-      break;
-    default:
-      return fail(E_ARG, "unknown epilogue");
-  }
+  RowsArgs a;
+  int rc = rows_args(d, epi, theta, image, tangent, image_t, io, a);
+  if (rc) return rc > 0 ? OK : rc;
   const BDims b = bf16_dims(d->n_in, d->n_out);
   const size_t shm = (size_t)b.fwd_words * 4 * (epi == MRL_EPI_FVP ? 2 : 1);
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(epi == MRL_EPI_PPOSGD ? 1 : rows_blocks_b(io->n, epi == MRL_EPI_FVP, io->partial != nullptr ? desc_cus(d) : 256)),
       blk(ROWS_BLOCK_B);
-  // the benchmark nets as static shapes (plain rows; a time-feature column built from
-  // ep_t takes the generic kernel); policy epilogues only for the policy shapes
-  int sh = 0;
-  if (!io->ep_t)
-    for (int i = 1; i < N_STATIC_SHAPES; ++i)
-      if (STATIC_SHAPES[i].O == d->n_in && STATIC_SHAPES[i].A == d->n_out && STATIC_SHAPES[i].head == d->head) sh = i;
-  // the value nets' prediction pass reads the time feature from ep_t (SH_TIME variants)
-  int sht = 0;
-  if (io->ep_t && epi == MRL_EPI_PROB && d->head == MRL_HEAD_LINEAR)
-    for (int i = 3; i <= 4; ++i)
-      if (STATIC_SHAPES[i].O == d->n_in && STATIC_SHAPES[i].A == d->n_out) sht = i | SH_TIME;
-  const bool pol = sh == 1 || sh == 2, vf = sh == 3 || sh == 4;
-#define MRL_ROWSB(EK, OK)                                                                                          \
-  do {                                                                                                             \
-    if ((OK) && sh == 1) hipLaunchKernelGGL((mlp_rows_bf16_kernel<EK, 1>), grid, blk, shm, s, a, b, image, image_t, skip); \
-    else if ((OK) && sh == 2) hipLaunchKernelGGL((mlp_rows_bf16_kernel<EK, 2>), grid, blk, shm, s, a, b, image, image_t, skip); \
-    else if ((OK) && sh == 3) hipLaunchKernelGGL((mlp_rows_bf16_kernel<EK, 3>), grid, blk, shm, s, a, b, image, image_t, skip); \
-    else if ((OK) && sh == 4) hipLaunchKernelGGL((mlp_rows_bf16_kernel<EK, 4>), grid, blk, shm, s, a, b, image, image_t, skip); \
-    else hipLaunchKernelGGL((mlp_rows_bf16_kernel<EK, 0>), grid, blk, shm, s, a, b, image, image_t, skip);               \
-  } while (0)
-  switch (epi) {
-    case MRL_EPI_PROB:
-      if (sht == (3 | SH_TIME)) hipLaunchKernelGGL((mlp_rows_bf16_kernel<MRL_EPI_PROB, 3 | SH_TIME>), grid, blk, shm, s, a, b, image, image_t, skip);
-      else if (sht == (4 | SH_TIME)) hipLaunchKernelGGL((mlp_rows_bf16_kernel<MRL_EPI_PROB, 4 | SH_TIME>), grid, blk, shm, s, a, b, image, image_t, skip);
-      else MRL_ROWSB(MRL_EPI_PROB, true);
-      break;
-    case MRL_EPI_LOSSES: MRL_ROWSB(MRL_EPI_LOSSES, pol); break;
-    case MRL_EPI_SURRGRAD: MRL_ROWSB(MRL_EPI_SURRGRAD, pol); break;
-    case MRL_EPI_VFLOSS: MRL_ROWSB(MRL_EPI_VFLOSS, vf); break;
-    case MRL_EPI_FVP:
-      if (a.cache_mode == MRL_CACHE_READ) MRL_ROWSB(EPI_FVP_CACHED_B, pol);
-      else MRL_ROWSB(MRL_EPI_FVP, pol);
-      break;
-    case MRL_EPI_PPOGRAD: MRL_ROWSB(MRL_EPI_PPOGRAD, pol); break;
-    case MRL_EPI_PPOSGD: MRL_ROWSB(MRL_EPI_PPOSGD, pol); break;
-  }
-#undef MRL_ROWSB
+  const int sh = static_shape_of(d, io->ep_t != nullptr, epi == MRL_EPI_PROB);
+  with_rows_epilogue(epi, a.cache_mode, [&](auto ek) {
+    constexpr int EK = decltype(ek)::value;
+    with_rows_shape<EK>(sh, [&](auto shape) {
+      hipLaunchKernelGGL((mlp_rows_bf16_kernel<EK, decltype(shape)::value>), grid, blk, shm, s, a, b, image, image_t, skip);
+    });
+  });
   return hip_check(hipGetLastError(), "mrl_mlp_rows_bf16");
 }
 
@@ -787,40 +604,8 @@ int mrl_mlp_vjp_bf16(const mrl_mlp_desc* d, const float* image, const float* x, 
   if (rc) return rc;
   if (!image || !x || !ghead || !slab) return fail(E_ARG, "null pointer");
   if (n <= 0) return OK;
-  VjpArgsB a{};
-  a.d = mlp_dims(d->n_in, d->n_out, d->head == MRL_HEAD_GAUSS);
-  a.b = bf16_dims(d->n_in, d->n_out);
-  a.n_obs = d->n_in - (ep_t ? 1 : 0);
-  a.n_sum = d->head == MRL_HEAD_GAUSS ? d->n_out : 0;
-  a.gh = d->n_out + a.n_sum;
-  a.x = x;
-  a.ept = ep_t;
-  a.ts_limit = ts_limit;
-  a.n = n;
-  a.ghead = ghead;
-  a.slab = slab;
-  a.cache = act_cache;
-  const size_t shm = (size_t)a.b.total_words * 4;
-  const dim3 grid(vjp_blocks_b(n, desc_cus(d))), blk(256);
-  hipStream_t s = (hipStream_t)stream;
-  // the benchmark policies and value nets as static shapes (plain rows only: the VF
-  // fit reads its materialised [obs, t / limit] rows; a time feature built from ep_t
-  // takes the generic kernel, which spills at the VF's shape)
-  int sh = 0;
-  if (!ep_t)
-    for (int i = 1; i < N_STATIC_SHAPES; ++i)
-      if (STATIC_SHAPES[i].O == d->n_in && STATIC_SHAPES[i].A == d->n_out && STATIC_SHAPES[i].head == d->head) sh = i;
-#define MRL_VJPB(C)                                                                                              \
-  do {                                                                                                           \
-    if (sh == 1) hipLaunchKernelGGL((mlp_vjp_bf16_kernel<C, 1>), grid, blk, shm, s, a, image, skip);              \
-    else if (sh == 2) hipLaunchKernelGGL((mlp_vjp_bf16_kernel<C, 2>), grid, blk, shm, s, a, image, skip);         \
-    else if (sh == 3) hipLaunchKernelGGL((mlp_vjp_bf16_kernel<C, 3>), grid, blk, shm, s, a, image, skip);         \
-    else if (sh == 4) hipLaunchKernelGGL((mlp_vjp_bf16_kernel<C, 4>), grid, blk, shm, s, a, image, skip);         \
-    else hipLaunchKernelGGL((mlp_vjp_bf16_kernel<C, 0>), grid, blk, shm, s, a, image, skip);                      \
-  } while (0)
-  if (act_cache != nullptr) MRL_VJPB(true);
-  else MRL_VJPB(false);
-#undef MRL_VJPB
+  launch_vjp_bf16(d, image, x, ep_t, ts_limit, ghead, n, slab, act_cache, vjp_blocks_b(n, desc_cus(d)), skip,
+                  (hipStream_t)stream);
   return hip_check(hipGetLastError(), "mrl_mlp_vjp_bf16");
 }
 

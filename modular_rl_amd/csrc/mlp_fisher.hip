@@ -143,7 +143,7 @@ __global__ __launch_bounds__(64 * HYB_WAVES, 1) void mlp_fisher_hyb_kernel(VjpAr
     if (wave < 4) {
       RowsArgs ra = fz.ra;
       BDims rb = fz.rb;
-      split_shape<SH>(ra, rb);
+      rows_shape<SH>(ra, rb);
       const MlpDims dd = head_dims(ra.d, rb);
       float ls[MAX_OUT], sd[MAX_OUT], dls[MAX_OUT];
 #pragma unroll
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(64 * HYB_WAVES, 1) void mlp_fisher_hyb_kernel(VjpAr
     if (wave < 4) {
       RowsArgs ra = fz.ra;
       BDims rb = fz.rb;
-      split_shape<SH>(ra, rb);
+      rows_shape<SH>(ra, rb);
       JvpSplitRole role;
       role.init(ra, rb, ldsx, ldsx + WS, lane);
       float sd[MAX_OUT], dls[MAX_OUT];
@@ -547,29 +547,8 @@ using namespace mrl;
 // inputs and images (each entry point adds its own fields of fz.ra and the tangent image)
 static void hyb_args(const mrl_mlp_desc* d, const float* theta, const float* image_s, const mrl_rows_io* io, float* slab,
                      int32_t cache_mode, VjpArgs& a, FisherFusedIn& fz) {
-  a.d = dims_of(d);
-  a.n_obs = d->n_in;
-  a.n_sum = d->head == MRL_HEAD_GAUSS ? d->n_out : 0;
-  a.gh = d->n_out + a.n_sum;
-  a.x = io->x;
-  a.ept = nullptr;
-  a.ts_limit = 1.0;
-  a.n = io->n;
-  a.ghead = nullptr;
-  a.slab = slab;
-  a.cache = io->act_cache;
-  RowsArgs& r = fz.ra;
-  r.d = a.d;
-  r.head = d->head;
-  r.n_obs = d->n_in;
-  r.gh = a.gh;
-  r.A = d->n_out;
-  r.x = io->x;
-  r.n = io->n;
-  r.inv_ng = io->inv_n_global;
-  r.logstd = d->head == MRL_HEAD_GAUSS ? theta + r.d.tls : nullptr;
-  r.cache = io->act_cache;
-  r.cache_mode = cache_mode;
+  a = vjp_args(d, io->x, nullptr, 1.0, nullptr, io->n, slab, io->act_cache);
+  fz.ra = rows_args_plain(d, theta, io, cache_mode);
   fz.rb = bf16_dims(d->n_in, d->n_out);
   fz.img_s = image_s;
 }
@@ -583,10 +562,10 @@ static int launch_hyb(const mrl_mlp_desc* d, const VjpArgs& a, const FisherFused
   const dim3 grid(grid_blocks(a.n, scaled_cap(VJP_MAX_BLOCKS, desc_cus(d)))), blk(64 * HYB_WAVES);
   const size_t shm = (size_t)split_fwd_words(fz.rb) * 4 * (PROD == 0 ? 2 : 1);
   hipStream_t s = (hipStream_t)stream;
-  switch (static_shape_of(d, false)) {
-    case 1: hipLaunchKernelGGL((mlp_fisher_hyb_kernel<1, PROD>), grid, blk, shm, s, a, image, skip, fz); break;
-    default: hipLaunchKernelGGL((mlp_fisher_hyb_kernel<2, PROD>), grid, blk, shm, s, a, image, skip, fz); break;
-  }
+  // mrl_mlp_fisher_hyb_fits leaves the policy shapes 1 and 2 only
+  with_static_shape<sh_bit(1), 2>(static_shape_of(d, false), [&](auto shape) {
+    hipLaunchKernelGGL((mlp_fisher_hyb_kernel<decltype(shape)::value, PROD>), grid, blk, shm, s, a, image, skip, fz);
+  });
   return hip_check(hipGetLastError(), what);
 }
 

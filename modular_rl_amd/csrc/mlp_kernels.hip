@@ -12,6 +12,8 @@
 //   mlp_vjp16.hip     mlp_vjp16_kernel      the transpose-free VJP on the activation cache.
 //   mlp_fisher.hip    mlp_fisher_hyb_kernel the one-pass Fisher product / policy gradient
 //                     (with its entry points).
+// The bf16 mode (mlp_bf16.hip) and the split-operand mode (mlp_split.hip) have their own
+// entry points; the argument checks and launch ladders all of them share are mlp_host.h's.
 //
 // Replaces the Theano-compiled functions of the reference: _act_prob
 // (core.py:269-270), compute_policy_gradient / compute_losses /
@@ -135,74 +137,6 @@ int mrl_mlp_pack(const mrl_mlp_desc* d, const float* theta, float* image, int32_
   return hip_check(hipGetLastError(), "mrl_mlp_pack");
 }
 
-// the RowsArgs of one row pass and the argument checks of its epilogue (mrl_mlp_rows,
-// mrl_mlp_rows_split); 1 = nothing to do (n <= 0)
-static int rows_args(const mrl_mlp_desc* d, int32_t epi, const float* theta, const float* image, const float* tangent,
-                     const float* image_t, const mrl_rows_io* io, RowsArgs& a) {
-  int rc = check_desc(d);
-  if (rc) return rc;
-  if (!io || !image || !io->x) return fail(E_ARG, "null pointer");
-  if (io->n <= 0) return 1;
-  a.d = dims_of(d);
-  a.head = d->head;
-  a.n_obs = d->n_in - (io->ep_t ? 1 : 0);
-  a.gh = d->head == MRL_HEAD_GAUSS ? 2 * d->n_out : d->n_out;
-  a.A = d->n_out;
-  a.x = io->x;
-  a.ept = io->ep_t;
-  a.ts_limit = io->timestep_limit;
-  a.n = io->n;
-  a.inv_ng = io->inv_n_global;
-  a.act = io->act;
-  a.adv = io->adv;
-  a.oldprob = io->oldprob;
-  a.target = io->target;
-  a.out = io->out;
-  a.ghead = io->ghead;
-  a.partial = io->partial;
-  a.logstd = (d->head == MRL_HEAD_GAUSS && theta) ? theta + a.d.tls : nullptr;
-  a.dlogstd = (d->head == MRL_HEAD_GAUSS && tangent) ? tangent + a.d.tls : nullptr;
-  a.kl_coeff = (float)io->kl_coeff;
-  a.kl_cutoff = (float)io->kl_cutoff;
-  a.cutoff_coeff = (float)io->cutoff_coeff;
-  a.reverse_kl = io->reverse_kl;
-  a.cache = io->act_cache;
-  a.cache_mode = io->act_cache != nullptr ? io->cache_mode : 0;
-  a.feat = io->feat_out;
-  if (a.feat != nullptr && (epi != MRL_EPI_PROB || io->ep_t == nullptr))
-    return fail(E_ARG, "feat_out is for MRL_EPI_PROB with ep_t (the value prediction)");
-  if (a.cache_mode == MRL_CACHE_READ && epi != MRL_EPI_FVP) return fail(E_ARG, "MRL_CACHE_READ is for MRL_EPI_FVP");
-  if (a.cache_mode == MRL_CACHE_WRITE && (epi == MRL_EPI_FVP || epi == MRL_EPI_PPOSGD))
-    return fail(E_ARG, "MRL_CACHE_WRITE is for the plain forward epilogues");
-  switch (epi) {
-    case MRL_EPI_PROB:
-      if (!io->out) return fail(E_ARG, "EPI_PROB needs out");
-      if (d->head == MRL_HEAD_GAUSS && !theta) return fail(E_ARG, "DiagGauss needs theta (logstd)");
-      break;
-    case MRL_EPI_LOSSES:
-    case MRL_EPI_SURRGRAD:
-    case MRL_EPI_PPOGRAD:
-    case MRL_EPI_PPOSGD:
-      if (d->head == MRL_HEAD_LINEAR) return fail(E_ARG, "policy epilogue on a value net");
-      if (!io->act || !io->adv || !io->oldprob || !io->partial) return fail(E_ARG, "losses need act/adv/oldprob/partial");
-      if (epi != MRL_EPI_LOSSES && !io->ghead) return fail(E_ARG, "gradient epilogues need ghead");
-      if (d->head == MRL_HEAD_GAUSS && !theta) return fail(E_ARG, "DiagGauss needs theta (logstd)");
-      if (epi == MRL_EPI_PPOSGD && io->n > MRL_PPO_BLOCK_ROWS) return fail(E_ARG, "PPOSGD minibatch exceeds one block");
-      break;
-    case MRL_EPI_VFLOSS:
-      if (d->head != MRL_HEAD_LINEAR || !io->target || !io->ghead || !io->partial)
-        return fail(E_ARG, "VFLOSS needs a linear head, target, ghead, partial");
-      break;
-    case MRL_EPI_FVP:
-      if (!tangent || !image_t || !io->ghead) return fail(E_ARG, "FVP needs tangent, image_t, ghead");
-      if (d->head == MRL_HEAD_GAUSS && !theta) return fail(E_ARG, "DiagGauss needs theta (logstd)");
-      break;
-    default:
-      return fail(E_ARG, "unknown epilogue");
-  }
-  return OK;
-}
-
 int mrl_mlp_rows(const mrl_mlp_desc* d, int32_t epi, const float* theta, const float* image, const float* tangent,
                  const float* image_t, const mrl_rows_io* io, const int32_t* skip, void* stream) {
   RowsArgs a;
@@ -238,18 +172,7 @@ int mrl_mlp_vjp(const mrl_mlp_desc* d, const float* image, const float* x, const
   if (rc) return rc;
   if (!image || !x || !ghead || !slab) return fail(E_ARG, "null pointer");
   if (n <= 0) return OK;
-  VjpArgs a;
-  a.d = dims_of(d);
-  a.n_obs = d->n_in - (ep_t ? 1 : 0);
-  a.n_sum = d->head == MRL_HEAD_GAUSS ? d->n_out : 0;
-  a.gh = d->n_out + a.n_sum;
-  a.x = x;
-  a.ept = ep_t;
-  a.ts_limit = ts_limit;
-  a.n = n;
-  a.ghead = ghead;
-  a.slab = slab;
-  a.cache = act_cache;
+  const VjpArgs a = vjp_args(d, x, ep_t, ts_limit, ghead, n, slab, act_cache);
   const int64_t blocks = grid_blocks(n, scaled_cap(VJP_MAX_BLOCKS, desc_cus(d)));
   // with a cache, the transpose-free 16-row kernel; it takes the bias gradient b0 through a
   // ones column of gW0's padding, so not at O % 16 == 0.  The 32-row kernel runs on the

@@ -18,34 +18,13 @@
 
 namespace mrl {
 
-constexpr int EPI_FVP_CACHED = 100;  // internal: MRL_EPI_FVP reading the activation cache
-
-// the kernel arguments with a static shape's dimensions substituted (compile-time
-// constants after inlining); SH == 0 leaves the run-time shape; SH | SH_TIME (mlp_layout.h)
-// keeps ep_t for the time-feature column
-template <int SH>
-__device__ inline RowsArgs rows_shape(const RowsArgs& in) {
-  RowsArgs a = in;
-  if constexpr ((SH & ~SH_TIME) != 0) {
-    constexpr int B = SH & ~SH_TIME;
-    constexpr StaticShape S = STATIC_SHAPES[B];
-    a.d = static_dims(B);
-    a.A = S.A;
-    a.head = S.head;
-    a.n_obs = (SH & SH_TIME) ? S.O - 1 : S.O;
-    a.gh = S.head == MRL_HEAD_GAUSS ? 2 * S.A : S.A;
-    if constexpr (!(SH & SH_TIME)) a.ept = nullptr;
-  }
-  return a;
-}
-
 template <int EPI_K, int SH>
 // 3 waves/SIMD: layer 2 is evaluated one M-tile at a time so the chain fits 168
 // registers (the cached Fisher-product pass took 176 at a bound of 2, i.e. 2 waves)
-__global__ __launch_bounds__(ROWS_BLOCK, 3) void mlp_rows_kernel(RowsArgs a_in, const float* __restrict__ img,
+__global__ __launch_bounds__(ROWS_BLOCK, 3) void mlp_rows_kernel(RowsArgs a, const float* __restrict__ img,
                                                                const float* __restrict__ imgt,
                                                                const int32_t* __restrict__ skip) {
-  const RowsArgs a = rows_shape<SH>(a_in);
+  rows_shape<SH>(a);
   constexpr bool CACHED = EPI_K == EPI_FVP_CACHED;
   constexpr int EPI = CACHED ? MRL_EPI_FVP : EPI_K;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -109,33 +88,13 @@ __global__ __launch_bounds__(ROWS_BLOCK, 3) void mlp_rows_kernel(RowsArgs a_in, 
 void launch_rows(int epi, int sh, const RowsArgs& a, const float* image, const float* image_t, int64_t blocks,
                  const int32_t* skip, hipStream_t s) {
   const size_t shm = (size_t)a.d.fwd_size * 4 * (epi == MRL_EPI_FVP ? 2 : 1);
-  const bool pol = sh == 1 || sh == 2, vf = sh == 3 || sh == 4;
   const dim3 grid(epi == MRL_EPI_PPOSGD ? 1 : blocks), blk(ROWS_BLOCK);
-#define MRL_ROWS_LAUNCH(EK, OK)                                                                                     \
-  do {                                                                                                              \
-    if ((OK) && sh == 1) hipLaunchKernelGGL((mlp_rows_kernel<EK, 1>), grid, blk, shm, s, a, image, image_t, skip); \
-    else if ((OK) && sh == 2) hipLaunchKernelGGL((mlp_rows_kernel<EK, 2>), grid, blk, shm, s, a, image, image_t, skip); \
-    else if ((OK) && sh == 3) hipLaunchKernelGGL((mlp_rows_kernel<EK, 3>), grid, blk, shm, s, a, image, image_t, skip); \
-    else if ((OK) && sh == 4) hipLaunchKernelGGL((mlp_rows_kernel<EK, 4>), grid, blk, shm, s, a, image, image_t, skip); \
-    else hipLaunchKernelGGL((mlp_rows_kernel<EK, 0>), grid, blk, shm, s, a, image, image_t, skip);                  \
-  } while (0)
-  switch (epi) {
-    case MRL_EPI_PROB:
-      if (sh == (3 | SH_TIME)) hipLaunchKernelGGL((mlp_rows_kernel<MRL_EPI_PROB, 3 | SH_TIME>), grid, blk, shm, s, a, image, image_t, skip);
-      else if (sh == (4 | SH_TIME)) hipLaunchKernelGGL((mlp_rows_kernel<MRL_EPI_PROB, 4 | SH_TIME>), grid, blk, shm, s, a, image, image_t, skip);
-      else MRL_ROWS_LAUNCH(MRL_EPI_PROB, true);
-      break;
-    case MRL_EPI_LOSSES: MRL_ROWS_LAUNCH(MRL_EPI_LOSSES, pol); break;
-    case MRL_EPI_SURRGRAD: MRL_ROWS_LAUNCH(MRL_EPI_SURRGRAD, pol); break;
-    case MRL_EPI_VFLOSS: MRL_ROWS_LAUNCH(MRL_EPI_VFLOSS, vf); break;
-    case MRL_EPI_FVP:
-      if (a.cache_mode == MRL_CACHE_READ) MRL_ROWS_LAUNCH(EPI_FVP_CACHED, pol);
-      else MRL_ROWS_LAUNCH(MRL_EPI_FVP, pol);
-      break;
-    case MRL_EPI_PPOGRAD: MRL_ROWS_LAUNCH(MRL_EPI_PPOGRAD, pol); break;
-    case MRL_EPI_PPOSGD: MRL_ROWS_LAUNCH(MRL_EPI_PPOSGD, pol); break;
-  }
-#undef MRL_ROWS_LAUNCH
+  with_rows_epilogue(epi, a.cache_mode, [&](auto ek) {
+    constexpr int EK = decltype(ek)::value;
+    with_rows_shape<EK>(sh, [&](auto shape) {
+      hipLaunchKernelGGL((mlp_rows_kernel<EK, decltype(shape)::value>), grid, blk, shm, s, a, image, image_t, skip);
+    });
+  });
 }
 
 // ------------------------------------------------------------------ VJP
@@ -465,14 +424,11 @@ void launch_vjp(const VjpArgs& a, const float* image, int64_t blocks, const int3
   const size_t shm = ((size_t)a.d.total_size + 4 * (size_t)SCR_FLOATS) * 4;
   const bool wide = a.d.O > 16;
   const dim3 grid(blocks), blk(256);
-#define MRL_VJP_LAUNCH(C)                                                                       \
-  do {                                                                                          \
-    if (!wide) hipLaunchKernelGGL((mlp_vjp_kernel<C, false>), grid, blk, shm, s, a, image, skip); \
-    else hipLaunchKernelGGL((mlp_vjp_kernel<C, true>), grid, blk, shm, s, a, image, skip);     \
-  } while (0)
-  if (a.cache != nullptr) MRL_VJP_LAUNCH(true);
-  else MRL_VJP_LAUNCH(false);
-#undef MRL_VJP_LAUNCH
+  with_bool(a.cache != nullptr, [&](auto cached) {
+    with_bool(wide, [&](auto w) {
+      hipLaunchKernelGGL((mlp_vjp_kernel<decltype(cached)::value, decltype(w)::value>), grid, blk, shm, s, a, image, skip);
+    });
+  });
 }
 
 }  // namespace mrl

@@ -60,7 +60,7 @@ __global__ __launch_bounds__(SPLIT_ROWS_BLOCK, (4 * MRL_SPLIT_FVP_OCC / SPLIT_RO
                                                  ? 4 * MRL_SPLIT_FVP_OCC / SPLIT_ROWS_WAVES : 1))
     void mlp_fvp_split_kernel(RowsArgs a, BDims b, const float* __restrict__ img_g, const float* __restrict__ imt_g,
                               const int32_t* __restrict__ skip) {
-  split_shape<SH>(a, b);
+  rows_shape<SH>(a, b);
   extern __shared__ __attribute__((aligned(16))) float lds[];
   if (skip != nullptr && *skip != 0) return;
   const int W = split_fwd_words(b);  // forward segments only
@@ -107,26 +107,11 @@ __global__ __launch_bounds__(SPLIT_ROWS_BLOCK, (4 * MRL_SPLIT_FVP_OCC / SPLIT_RO
 // as mlp_rows_kernel<EPI> to f32 rounding (the products are exact, the summation order
 // differs); the activation cache it writes (SURRGRAD / VFLOSS, MRL_CACHE_WRITE) has the
 // f32 kernel's layout, so the Fisher products and VJPs read it unchanged.
-template <int SH>
-__device__ inline void split_rows_shape(RowsArgs& a, BDims& b) {
-  if constexpr ((SH & ~SH_TIME) != 0) {
-    constexpr int B = SH & ~SH_TIME;
-    constexpr StaticShape S = STATIC_SHAPES[B];
-    a.d = static_dims(B);
-    a.A = S.A;
-    a.head = S.head;
-    a.n_obs = (SH & SH_TIME) ? S.O - 1 : S.O;
-    a.gh = S.head == MRL_HEAD_GAUSS ? 2 * S.A : S.A;
-    if constexpr (!(SH & SH_TIME)) a.ept = nullptr;
-    b = bf16_dims(S.O, S.A);
-  }
-}
-
 template <int EPI, int SH>
 __global__ __launch_bounds__(SPLIT_ROWS_BLOCK, 2) void mlp_rows_split_kernel(RowsArgs a, BDims b,
                                                                             const float* __restrict__ img_g,
                                                                             const int32_t* __restrict__ skip) {
-  split_rows_shape<SH>(a, b);
+  rows_shape<SH>(a, b);
   extern __shared__ __attribute__((aligned(16))) float lds[];
   if (skip != nullptr && *skip != 0) return;
   const int W = split_fwd_words(b);
@@ -172,36 +157,20 @@ int launch_rows_split(int epi, int sh, const RowsArgs& a, const BDims& b, const 
   const dim3 grid(blocks), blk(SPLIT_ROWS_BLOCK);
   const size_t shm = (size_t)split_fwd_words(b) * 4;
   hipStream_t s = (hipStream_t)stream;
-#define MRL_RS(E, S) hipLaunchKernelGGL((mlp_rows_split_kernel<E, S>), grid, blk, shm, s, a, b, image_s, skip)
+  auto launch = [&](auto e) {
+    constexpr int E = decltype(e)::value;
+    with_static_shape<rows_shapes(E)>(sh, [&](auto shape) {
+      hipLaunchKernelGGL((mlp_rows_split_kernel<E, decltype(shape)::value>), grid, blk, shm, s, a, b, image_s, skip);
+    });
+  };
   switch (epi) {
-    case MRL_EPI_PROB:
-      if (sh == 1) MRL_RS(MRL_EPI_PROB, 1);
-      else if (sh == 2) MRL_RS(MRL_EPI_PROB, 2);
-      else if (sh == 3) MRL_RS(MRL_EPI_PROB, 3);
-      else if (sh == 4) MRL_RS(MRL_EPI_PROB, 4);
-      else if (sh == (3 | SH_TIME)) MRL_RS(MRL_EPI_PROB, 3 | SH_TIME);
-      else if (sh == (4 | SH_TIME)) MRL_RS(MRL_EPI_PROB, 4 | SH_TIME);
-      else MRL_RS(MRL_EPI_PROB, 0);
-      break;
-    case MRL_EPI_LOSSES:
-      if (sh == 1) MRL_RS(MRL_EPI_LOSSES, 1);
-      else if (sh == 2) MRL_RS(MRL_EPI_LOSSES, 2);
-      else MRL_RS(MRL_EPI_LOSSES, 0);
-      break;
-    case MRL_EPI_SURRGRAD:
-      if (sh == 1) MRL_RS(MRL_EPI_SURRGRAD, 1);
-      else if (sh == 2) MRL_RS(MRL_EPI_SURRGRAD, 2);
-      else MRL_RS(MRL_EPI_SURRGRAD, 0);
-      break;
-    case MRL_EPI_VFLOSS:
-      if (sh == 3) MRL_RS(MRL_EPI_VFLOSS, 3);
-      else if (sh == 4) MRL_RS(MRL_EPI_VFLOSS, 4);
-      else MRL_RS(MRL_EPI_VFLOSS, 0);
-      break;
+    case MRL_EPI_PROB: launch(std::integral_constant<int, MRL_EPI_PROB>{}); break;
+    case MRL_EPI_LOSSES: launch(std::integral_constant<int, MRL_EPI_LOSSES>{}); break;
+    case MRL_EPI_SURRGRAD: launch(std::integral_constant<int, MRL_EPI_SURRGRAD>{}); break;
+    case MRL_EPI_VFLOSS: launch(std::integral_constant<int, MRL_EPI_VFLOSS>{}); break;
     default:
       return fail(E_UNSUPPORTED, "mrl_mlp_rows_split: epilogue");
   }
-#undef MRL_RS
   return hip_check(hipGetLastError(), "mrl_mlp_rows_split");
 }
 
@@ -253,29 +222,16 @@ int mrl_mlp_fvp_split(const mrl_mlp_desc* d, const float* theta, const float* im
   if (d->head == MRL_HEAD_LINEAR) return fail(E_ARG, "Fisher product of a value net");
   if (d->head == MRL_HEAD_GAUSS && !theta) return fail(E_ARG, "DiagGauss needs theta (logstd)");
   if (io->n <= 0) return OK;
-  RowsArgs a{};
-  a.d = dims_of(d);
-  a.head = d->head;
-  a.n_obs = d->n_in;
-  a.gh = d->head == MRL_HEAD_GAUSS ? 2 * d->n_out : d->n_out;
-  a.A = d->n_out;
-  a.x = io->x;
-  a.n = io->n;
-  a.inv_ng = io->inv_n_global;
+  RowsArgs a = rows_args_plain(d, theta, io, MRL_CACHE_READ);
   a.ghead = io->ghead;
-  a.logstd = (d->head == MRL_HEAD_GAUSS && theta) ? theta + a.d.tls : nullptr;
-  a.dlogstd = (d->head == MRL_HEAD_GAUSS && tangent) ? tangent + a.d.tls : nullptr;
-  a.cache = io->act_cache;
-  a.cache_mode = MRL_CACHE_READ;
+  a.dlogstd = d->head == MRL_HEAD_GAUSS ? tangent + a.d.tls : nullptr;
   const BDims b = bf16_dims(d->n_in, d->n_out);
   const size_t shm = (size_t)split_fwd_words(b) * 4 * 2;
   const dim3 grid(split_rows_blocks(io->n)), blk(SPLIT_ROWS_BLOCK);
   hipStream_t s = (hipStream_t)stream;
-  switch (static_shape_of(d, false)) {
-    case 1: hipLaunchKernelGGL((mlp_fvp_split_kernel<1>), grid, blk, shm, s, a, b, image, image_t, skip); break;
-    case 2: hipLaunchKernelGGL((mlp_fvp_split_kernel<2>), grid, blk, shm, s, a, b, image, image_t, skip); break;
-    default: hipLaunchKernelGGL((mlp_fvp_split_kernel<0>), grid, blk, shm, s, a, b, image, image_t, skip); break;
-  }
+  with_static_shape<SH_POLICY>(static_shape_of(d, false), [&](auto shape) {
+    hipLaunchKernelGGL((mlp_fvp_split_kernel<decltype(shape)::value>), grid, blk, shm, s, a, b, image, image_t, skip);
+  });
   return hip_check(hipGetLastError(), "mrl_mlp_fvp_split");
 }
 

@@ -1,7 +1,8 @@
-// Per-row epilogues shared by the fused 64-wide rows kernel (mlp_rows_vjp.hip) and the
-// layered-path head kernel (gemm.hip): given the head pre-activation z (and its
-// tangent dz for the Fisher product) of one row, produce prob rows, the surrogate /
-// KL / entropy partial sums, the head-gradient row, or the VF squared error.
+// Per-row epilogues shared by the fused 64-wide rows kernels (mlp_rows_vjp.hip, mlp_bf16.hip,
+// mlp_split.hip, mlp_fisher.hip) and the layered-path head kernel (gemm.hip): given the
+// head pre-activation z (and its tangent dz for the Fisher product) of one row, produce
+// prob rows, the surrogate / KL / entropy partial sums, the head-gradient row, or the VF
+// squared error.  Also the fused rows kernels' static-shape substitution.
 #pragma once
 #include "../../include/mrl_hip.h"
 #include "mlp_device.h"
@@ -34,6 +35,25 @@ struct RowsArgs {
   int cache_mode;        // MRL_CACHE_WRITE: the forward stores h1/h2; MRL_CACHE_READ: FVP reads them
   float* feat;           // EPI_PROB with ep_t: the input rows [obs, t / limit] written beside the values
 };
+
+constexpr int EPI_FVP_CACHED = 100;  // internal: MRL_EPI_FVP reading the activation cache
+
+// the kernel arguments with a static shape's dimensions substituted (compile-time
+// constants after inlining); SH == 0 leaves the run-time shape; SH | SH_TIME (mlp_layout.h)
+// keeps ep_t for the time-feature column.  (With the bf16 image's BDims: bf16_frag.h.)
+template <int SH>
+__device__ inline void rows_shape(RowsArgs& a) {
+  if constexpr ((SH & ~SH_TIME) != 0) {
+    constexpr int B = SH & ~SH_TIME;
+    constexpr StaticShape S = STATIC_SHAPES[B];
+    a.d = static_dims(B);
+    a.A = S.A;
+    a.head = S.head;
+    a.n_obs = (SH & SH_TIME) ? S.O - 1 : S.O;
+    a.gh = S.head == MRL_HEAD_GAUSS ? 2 * S.A : S.A;
+    if constexpr (!(SH & SH_TIME)) a.ept = nullptr;
+  }
+}
 
 // [obs, t / timestep_limit] of one row (the VF fit's materialised features, core.py:659-660)
 // written by the value prediction that reads them anyway: lane half h writes columns

@@ -184,6 +184,119 @@ def test_gemm_refuses_bad_descriptors():
     assert tile(m=513, n=512, k=65536, epilogue=_lib.GEMM_SLAB, splits=4) == 32
 
 
+_ROWS_ENTRIES = ["mrl_mlp_rows", "mrl_mlp_rows_bf16", "mrl_mlp_rows_split"]
+_PTR = 0x10000  # a non-null address: nothing is dereferenced before the argument checks return
+_SPLIT_EPIS = (0, 1, 2, 3)  # PROB, LOSSES, SURRGRAD, VFLOSS: what mrl_mlp_rows_split takes
+_E_ARG, _E_UNSUPPORTED = -1, -2
+
+# (id, epi, head, argument changes, mrl_last_error text); every case starts from a call whose
+# arguments are all valid for its epilogue and head.  Keys of the changes: a mrl_rows_io
+# field, or "io" / "theta" / "image" / "tangent" / "image_t" (None: a null pointer).
+_ROWS_REJECTS = [
+    ("null_io", 0, 1, {"io": None}, "null pointer"),
+    ("null_image", 0, 1, {"image": None}, "null pointer"),
+    ("null_x", 0, 1, {"x": None}, "null pointer"),
+    ("feat_out_not_prob", 3, 0, {"ep_t": _PTR, "feat_out": _PTR},
+     "feat_out is for MRL_EPI_PROB with ep_t (the value prediction)"),
+    ("feat_out_no_ep_t", 0, 0, {"feat_out": _PTR}, "feat_out is for MRL_EPI_PROB with ep_t (the value prediction)"),
+    ("cache_read_not_fvp", 0, 1, {"act_cache": _PTR, "cache_mode": 2}, "MRL_CACHE_READ is for MRL_EPI_FVP"),
+    ("cache_write_fvp", 4, 1, {"act_cache": _PTR, "cache_mode": 1}, "MRL_CACHE_WRITE is for the plain forward epilogues"),
+    ("cache_write_pposgd", 6, 1, {"act_cache": _PTR, "cache_mode": 1},
+     "MRL_CACHE_WRITE is for the plain forward epilogues"),
+    ("prob_no_out", 0, 1, {"out": None}, "EPI_PROB needs out"),
+    ("prob_gauss_no_theta", 0, 2, {"theta": None}, "DiagGauss needs theta (logstd)"),
+    ("losses_gauss_no_theta", 1, 2, {"theta": None}, "DiagGauss needs theta (logstd)"),
+    ("fvp_gauss_no_theta", 4, 2, {"theta": None}, "DiagGauss needs theta (logstd)"),
+    ("losses_linear_head", 1, 0, {}, "policy epilogue on a value net"),
+    ("surrgrad_linear_head", 2, 0, {}, "policy epilogue on a value net"),
+    ("ppograd_linear_head", 5, 0, {}, "policy epilogue on a value net"),
+    ("pposgd_linear_head", 6, 0, {}, "policy epilogue on a value net"),
+    ("losses_no_act", 1, 1, {"act": None}, "losses need act/adv/oldprob/partial"),
+    ("losses_no_adv", 1, 2, {"adv": None}, "losses need act/adv/oldprob/partial"),
+    ("surrgrad_no_oldprob", 2, 1, {"oldprob": None}, "losses need act/adv/oldprob/partial"),
+    ("ppograd_no_partial", 5, 1, {"partial": None}, "losses need act/adv/oldprob/partial"),
+    ("surrgrad_no_ghead", 2, 1, {"ghead": None}, "gradient epilogues need ghead"),
+    ("pposgd_no_ghead", 6, 2, {"ghead": None}, "gradient epilogues need ghead"),
+    ("pposgd_too_many_rows", 6, 1, {"n": 128 + 1}, "PPOSGD minibatch exceeds one block"),
+    ("vfloss_policy_head", 3, 1, {}, "VFLOSS needs a linear head, target, ghead, partial"),
+    ("vfloss_no_target", 3, 0, {"target": None}, "VFLOSS needs a linear head, target, ghead, partial"),
+    ("vfloss_no_ghead", 3, 0, {"ghead": None}, "VFLOSS needs a linear head, target, ghead, partial"),
+    ("vfloss_no_partial", 3, 0, {"partial": None}, "VFLOSS needs a linear head, target, ghead, partial"),
+    ("fvp_no_tangent", 4, 1, {"tangent": None}, "FVP needs tangent, image_t, ghead"),
+    ("fvp_no_image_t", 4, 2, {"image_t": None}, "FVP needs tangent, image_t, ghead"),
+    ("fvp_no_ghead", 4, 1, {"ghead": None}, "FVP needs tangent, image_t, ghead"),
+    ("unknown_epilogue", 7, 1, {}, "unknown epilogue"),
+]
+
+
+def _rows_call(lib, entry, epi, head, changes):
+    """One rows entry point on a valid 64 x 64 descriptor, n = 8, dummy non-null addresses."""
+    from modular_rl_amd import _lib
+    assert _lib.PPO_BLOCK_ROWS == 128
+    d = _lib.MlpDesc(12 if head == _lib.HEAD_LINEAR else 11, 1 if head == _lib.HEAD_LINEAR else 3, head, 64, 2)
+    io = _lib.RowsIO(x=_PTR, ep_t=None, timestep_limit=1.0, n=8, inv_n_global=0.125, act=_PTR, adv=_PTR, oldprob=_PTR,
+                     target=_PTR, out=_PTR, ghead=_PTR, partial=_PTR, cache_mode=0, act_cache=None, feat_out=None)
+    top = {"io": ctypes.byref(io), "theta": _PTR, "image": _PTR, "tangent": _PTR, "image_t": _PTR}
+    for k, v in changes.items():
+        if k in top:
+            top[k] = v
+        else:
+            setattr(io, k, v)
+    if entry == "mrl_mlp_rows_split":
+        return getattr(lib, entry)(ctypes.byref(d), epi, top["theta"], top["image"], top["io"], None, None)
+    return getattr(lib, entry)(ctypes.byref(d), epi, top["theta"], top["image"], top["tangent"], top["image_t"],
+                               top["io"], None, None)
+
+
+@pytest.mark.parametrize("entry", _ROWS_ENTRIES)
+@pytest.mark.parametrize("case", _ROWS_REJECTS, ids=[c[0] for c in _ROWS_REJECTS])
+def test_rows_entry_points_reject_bad_arguments(entry, case):
+    """Every rejecting condition of the rows passes' shared argument checks, per entry point:
+    the status and the exact mrl_last_error text.  The checks return before any launch, so
+    this runs without a GPU.  mrl_mlp_rows_split refuses the epilogues it does not take
+    before anything else."""
+    from modular_rl_amd import _lib
+    lib = _lib.load()
+    _, epi, head, changes, text = case
+    rc = _rows_call(lib, entry, epi, head, changes)
+    if entry == "mrl_mlp_rows_split" and epi not in _SPLIT_EPIS:
+        assert rc == _E_UNSUPPORTED
+        assert lib.mrl_last_error() == b"mrl_mlp_rows_split: PROB, LOSSES, SURRGRAD or VFLOSS"
+    else:
+        assert rc == _E_ARG
+        assert lib.mrl_last_error() == text.encode()
+
+
+@pytest.mark.parametrize("entry", _ROWS_ENTRIES)
+def test_rows_entry_points_accept_zero_rows(entry):
+    """n = 0 with otherwise valid arguments: nothing to do, status 0, for every epilogue."""
+    from modular_rl_amd import _lib
+    lib = _lib.load()
+    for epi, head in [(0, 0), (0, 1), (0, 2), (1, 1), (2, 2), (3, 0), (4, 1), (5, 2), (6, 1)]:
+        if entry == "mrl_mlp_rows_split" and epi not in _SPLIT_EPIS:
+            continue
+        assert _rows_call(lib, entry, epi, head, {"n": 0}) == 0, (epi, head)
+
+
+@pytest.mark.parametrize("entry", ["mrl_mlp_vjp", "mrl_mlp_vjp_bf16"])
+def test_vjp_entry_points_reject_null_pointers(entry):
+    from modular_rl_amd import _lib
+    lib = _lib.load()
+    d = _lib.MlpDesc(11, 3, _lib.HEAD_GAUSS, 64, 2)
+    # image, x, ep_t, ts_limit, ghead, n, slab, act_cache, skip, stream
+    good = [_PTR, _PTR, None, 1.0, _PTR, 8, _PTR, None, None, None]
+    for i in (0, 1, 4, 6):
+        args = list(good)
+        args[i] = None
+        assert getattr(lib, entry)(ctypes.byref(d), *args) == _E_ARG, i
+        assert lib.mrl_last_error() == b"null pointer"
+    assert getattr(lib, entry)(None, *good) == _E_ARG
+    assert lib.mrl_last_error() == b"null mlp desc"
+    args = list(good)
+    args[5] = 0
+    assert getattr(lib, entry)(ctypes.byref(d), *args) == 0
+
+
 _UBSAN_PROBE = r"""
 import ctypes, sys
 from modular_rl_amd import _lib

@@ -1,4 +1,6 @@
-"""GPU checks of the bf16 throughput mode (MRL_COMPUTE_BF16) through the C ABI.
+"""GPU checks of the bf16 throughput mode (MRL_COMPUTE_BF16) through the C ABI: the fused
+kernels of csrc/mlp_bf16.hip (rows and VJP in one unit, their tile forward / JVP in
+mlp_bf16_device.h, host glue shared with the f32 units in mlp_host.h) and the bf16 GEMMs.
 
 fp32 is the parity dtype (north_star: 1e-4 relative); bf16 rounds the MFMA operands
 (weights, layer inputs, backpropagated rows) to bf16 and accumulates in f32.  Two
@@ -32,7 +34,7 @@ def _rel(a, b):
     return np.abs(a - b).max() / max(np.abs(b).max(), 1e-30)
 
 
-# ---- float64 emulation of csrc/mlp_bf16.hip's rounding points (fused 64-wide net)
+# ---- float64 emulation of the rounding points of csrc/mlp_bf16.hip and mlp_bf16_device.h (fused 64-wide net)
 def emu_forward(spec, th, x):
     (W0, W1, W2), (b0, b1, b2), _ = spec.split(th)
     xb = bfr(x)
@@ -189,6 +191,33 @@ def test_bf16_losses_and_policy_gradient(head, nin, nout):
     assert _rel(g.cpu().numpy(), T.policy_gradient(spec, th, ob, act, adv, oldprob)) < 5e-2
 
 
+@pytest.mark.parametrize("head,nin,nout", CASES)
+def test_bf16_losses_pass(head, nin, nout):
+    """The LOSSES pass (the line search's: no head rows, no cache) on the static policy
+    shapes and the run-time shape: its surr / KL / entropy sums against the oracle at the
+    bound of the test above."""
+    from modular_rl_amd import _lib
+    N = 293
+    rng, spec, th, ob = _setup(head, nin, nout, N, 4)
+    oldth = th + 0.01 * rng.standard_normal(spec.P)
+    oldprob = T.policy_prob(spec, oldth, ob).astype(np.float32).astype(np.float64)
+    noise = rng.standard_normal((N, nout)) if head == "gauss" else rng.random(N)
+    act = T.sample(spec, oldprob, noise)
+    if head == "gauss":
+        act = act.astype(np.float32).astype(np.float64)
+    adv = rng.standard_normal(N).astype(np.float32).astype(np.float64)
+    net = _net(head, nin, nout)
+    net.set_flat(th)
+    partial = torch.zeros(net.partial_rows(N) * 4, dtype=torch.float64, device="cuda")
+    net.rows(_lib.EPI_LOSSES, _dev(ob), N, inv_n_global=1.0 / N,
+             act=_dev(act, torch.int32 if head == "softmax" else torch.float32), adv=_dev(adv), oldprob=_dev(oldprob),
+             partial=partial)
+    sums = torch.zeros(4, dtype=torch.float64, device="cuda")
+    s = net.reduce_partial(partial, N, sums).cpu().numpy()
+    losses = np.array([-s[0] / N, s[1] / N, s[2] / N])
+    np.testing.assert_allclose(losses, T.surr_kl_ent(spec, th, ob, act, adv, oldprob), rtol=BF16_ORACLE_RTOL, atol=2e-3)
+
+
 def test_bf16_value_loss_grad_with_time_feature():
     from modular_rl_amd import _lib
     N, nin, limit = 3000, 12, 200.0
@@ -215,6 +244,107 @@ def test_bf16_value_loss_grad_with_time_feature():
     want_g = want_g - 2.0 * T.VF_L2 * th  # the kernel's part: the MSE gradient (L2 is added on the host)
     assert _rel(g.cpu().numpy(), emu) < BF16_EMU_RTOL
     assert _rel(g.cpu().numpy(), want_g) < BF16_ORACLE_RTOL
+
+
+# The value nets' static-shape kernels (mlp_layout.h shapes 3 and 4: [obs, t / limit] ->
+# value for Hopper-v2 and CartPole-v0).  293 rows = two 128-row blocks and a 37-row tail:
+# full tiles, one partial tile, and waves that get no tile.
+VALUE_SHAPES = [12, 5]
+VALUE_N, VALUE_LIMIT = 293, 200.0
+_value_refs = {}
+
+
+def _value_ref(nin):
+    """Inputs, float64 emulation and oracle of one value shape, computed once per shape and
+    shared (read-only) by the tests below."""
+    if nin not in _value_refs:
+        N = VALUE_N
+        rng = np.random.default_rng(40 + nin)
+        spec = T.Spec(nin, [64, 64], 1, "linear")
+        th = (T.mlp_init(rng, spec.shapes, False) + 0.05 * rng.standard_normal(spec.P)).astype(np.float32)
+        th = th.astype(np.float64)
+        ob = rng.standard_normal((N, nin - 1)).astype(np.float32).astype(np.float64)
+        ept = rng.integers(0, 200, N)
+        tf = (ept / VALUE_LIMIT).astype(np.float32).astype(np.float64)  # the kernels' f32 time feature
+        X = np.concatenate([ob, tf[:, None]], axis=1)
+        y = rng.standard_normal(N).astype(np.float32).astype(np.float64)
+        z, acts = emu_forward(spec, th, X)
+        want_z, _ = T.mlp_forward(spec, th, X)
+        _, want_g, want_mse, _ = T.vf_loss_grad(spec, th, X, y)
+        ref = dict(spec=spec, th=th, ob=ob, ept=ept, X=X, y=y, z=z[:, 0], want_z=want_z[:, 0],
+                   emu_mse=np.sum((z[:, 0] - y) ** 2) / N, want_mse=want_mse,
+                   emu_g=emu_vjp(spec, th, acts, 2.0 * (z - y[:, None]) / N),
+                   want_g=want_g - 2.0 * T.VF_L2 * th)  # the kernel's part (L2 is added on the host)
+        for v in ref.values():
+            if isinstance(v, np.ndarray):
+                v.setflags(write=False)
+        _value_refs[nin] = ref
+    return _value_refs[nin]
+
+
+@pytest.mark.parametrize("nin", VALUE_SHAPES)
+def test_bf16_value_shapes_plain_rows(nin):
+    """Plain [obs, t / limit] rows of the value shapes: the prediction (PROB), the loss rows
+    (VFLOSS, writing the activation cache) and the VJP of their head rows from the cache
+    and with the forward recomputed -- the static-shape instantiations 3 and 4 of the rows
+    and of both VJP kernels."""
+    from modular_rl_amd import _lib
+    r = _value_ref(nin)
+    N = VALUE_N
+    net = _net("linear", nin, 1)
+    net.set_flat(r["th"])
+    x = _dev(r["X"])
+    got = net.forward(x, N).cpu().numpy().astype(np.float64)
+    assert got.shape == (N,)
+    assert _rel(got, r["z"]) < BF16_EMU_RTOL, _rel(got, r["z"])
+    assert _rel(got, r["want_z"]) < BF16_ORACLE_RTOL, _rel(got, r["want_z"])
+    partial = torch.zeros(net.partial_rows(N) * 4, dtype=torch.float64, device="cuda")
+    ghead = torch.zeros(N, dtype=torch.float32, device="cuda")
+    net.rows(_lib.EPI_VFLOSS, x, N, inv_n_global=1.0 / N, target=_dev(r["y"]), ghead=ghead, partial=partial)
+    sums = torch.zeros(4, dtype=torch.float64, device="cuda")
+    net.reduce_partial(partial, N, sums)
+    mse = sums.cpu().numpy()[0] / N
+    assert abs(mse - r["emu_mse"]) < BF16_EMU_RTOL * r["emu_mse"], (mse, r["emu_mse"])
+    assert abs(mse - r["want_mse"]) < BF16_ORACLE_RTOL * r["want_mse"], (mse, r["want_mse"])
+    gh = ghead.cpu().numpy().astype(np.float64)
+    assert _rel(gh, 2.0 * (r["z"] - r["y"]) / N) < BF16_EMU_RTOL
+    got_g = {}
+    for cached in (True, False):
+        net.use_cache = cached
+        g = torch.zeros(net.P, dtype=torch.float32, device="cuda")
+        net.vjp_flat(x, N, ghead, g)
+        got_g[cached] = g.cpu().numpy().astype(np.float64)
+    net.use_cache = True
+    # the emulated VJP of the kernel's own head rows, and the oracle
+    spec, th = r["spec"], r["th"]
+    _, acts = emu_forward(spec, th, r["X"])
+    emu = emu_vjp(spec, th, acts, gh[:, None])
+    for cached, g in got_g.items():
+        assert _rel(g, emu) < BF16_EMU_RTOL, (cached, _rel(g, emu))
+        assert _rel(g, r["emu_g"]) < BF16_EMU_RTOL, (cached, _rel(g, r["emu_g"]))
+        assert _rel(g, r["want_g"]) < BF16_ORACLE_RTOL, (cached, _rel(g, r["want_g"]))
+    # the cached pass reads exactly the activations the uncached one recomputes
+    assert _rel(got_g[True], got_g[False]) < 1e-6
+
+
+@pytest.mark.parametrize("feat", [False, True])
+@pytest.mark.parametrize("nin", VALUE_SHAPES)
+def test_bf16_value_shapes_prediction_with_time_feature(nin, feat):
+    """The value prediction straight from the rollout's rows (obs and ep_t: the SH_TIME
+    instantiations of shapes 3 and 4), with and without the feature rows written beside
+    the values."""
+    r = _value_ref(nin)
+    N = VALUE_N
+    net = _net("linear", nin, 1)
+    net.set_flat(r["th"])
+    fo = torch.full((N, nin), float("nan"), dtype=torch.float32, device="cuda") if feat else None
+    got = net.forward(_dev(r["ob"]), N, ep_t=_dev(r["ept"], torch.int32), timestep_limit=VALUE_LIMIT, feat_out=fo)
+    got = got.cpu().numpy().astype(np.float64)
+    assert got.shape == (N,)
+    assert _rel(got, r["z"]) < BF16_EMU_RTOL, _rel(got, r["z"])
+    assert _rel(got, r["want_z"]) < BF16_ORACLE_RTOL, _rel(got, r["want_z"])
+    if feat:  # [obs, t / limit] in f32, exactly
+        assert np.array_equal(fo.cpu().numpy(), r["X"].astype(np.float32))
 
 
 def test_bf16_gemm_exact_on_rounded_operands():
