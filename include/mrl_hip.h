@@ -78,7 +78,10 @@ int mrl_mlp_pack(const mrl_mlp_desc* d, const float* theta, float* image, int32_
 
 typedef struct {
   const float* x;          /* [N, n_obs] observations                              */
-  const int32_t* ep_t;     /* [N] step index in episode (VF time feature) or NULL  */
+  const int32_t* ep_t;     /* [N] step index in episode (VF time feature) or NULL;
+                            * with ep_t, x has n_obs = n_in - 1 columns and the net
+                            * needs n_in >= 2 (n_in == 1: MRL_E_ARG, here and in
+                            * mrl_mlp_vjp / mrl_mlp_vjp_bf16)                      */
   double timestep_limit;   /* time feature = ep_t / timestep_limit (core.py:660)   */
   int64_t n;               /* rows                                                 */
   double inv_n_global;     /* 1 / rows summed over all ranks                       */

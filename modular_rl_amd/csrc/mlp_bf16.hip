@@ -603,6 +603,7 @@ int mrl_mlp_vjp_bf16(const mrl_mlp_desc* d, const float* image, const float* x, 
   int rc = check_desc(d);
   if (rc) return rc;
   if (!image || !x || !ghead || !slab) return fail(E_ARG, "null pointer");
+  if ((rc = check_time_feature(d, ep_t)) != OK) return rc;
   if (n <= 0) return OK;
   launch_vjp_bf16(d, image, x, ep_t, ts_limit, ghead, n, slab, act_cache, vjp_blocks_b(n, desc_cus(d)), skip,
                   (hipStream_t)stream);

@@ -45,6 +45,15 @@ inline int check_desc(const mrl_mlp_desc* d) {
   return OK;
 }
 
+// a time feature built from ep_t sits beside n_in - 1 observation columns, and the clamped
+// column loads of the kernels (load_x, XGlobalNB) read column n_obs - 1: a net of the time
+// feature alone (n_in == 1) has none
+inline int check_time_feature(const mrl_mlp_desc* d, const int32_t* ep_t) {
+  if (ep_t != nullptr && d->n_in < 2)
+    return fail(E_ARG, "a time-feature net (ep_t) needs n_in >= 2: n_obs = n_in - 1 observation columns (got n_obs = 0)");
+  return OK;
+}
+
 inline MlpDims dims_of(const mrl_mlp_desc* d) { return mlp_dims(d->n_in, d->n_out, d->head == MRL_HEAD_GAUSS); }
 
 // the static shape (mlp_layout.h) a launch matches, or 0: plain rows only (a time
@@ -148,6 +157,7 @@ inline int rows_args(const mrl_mlp_desc* d, int32_t epi, const float* theta, con
   int rc = check_desc(d);
   if (rc) return rc;
   if (!io || !image || !io->x) return fail(E_ARG, "null pointer");
+  if ((rc = check_time_feature(d, io->ep_t)) != OK) return rc;
   if (io->n <= 0) return 1;
   a = rows_args_plain(d, theta, io, io->act_cache != nullptr ? io->cache_mode : 0);
   a.n_obs = d->n_in - (io->ep_t ? 1 : 0);

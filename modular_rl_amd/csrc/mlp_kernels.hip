@@ -171,6 +171,7 @@ int mrl_mlp_vjp(const mrl_mlp_desc* d, const float* image, const float* x, const
   int rc = check_desc(d);
   if (rc) return rc;
   if (!image || !x || !ghead || !slab) return fail(E_ARG, "null pointer");
+  if ((rc = check_time_feature(d, ep_t)) != OK) return rc;
   if (n <= 0) return OK;
   const VjpArgs a = vjp_args(d, x, ep_t, ts_limit, ghead, n, slab, act_cache);
   const int64_t blocks = grid_blocks(n, scaled_cap(VJP_MAX_BLOCKS, desc_cus(d)));
@@ -202,6 +203,7 @@ int mrl_linesearch_eval(const mrl_mlp_desc* pol, int32_t compute, const float* t
   int rc = check_desc(pol);
   if (rc) return rc;
   if (!io || !cand || !images || !partials || !out) return fail(E_ARG, "mrl_linesearch_eval: null pointer");
+  if ((rc = check_time_feature(pol, io->ep_t)) != OK) return rc;
   if (compute != MRL_COMPUTE_F32 && compute != MRL_COMPUTE_BF16 && compute != MRL_COMPUTE_SPLIT)
     return fail(E_ARG, "bad compute");
   const bool bf = compute == MRL_COMPUTE_BF16, sp = compute == MRL_COMPUTE_SPLIT;

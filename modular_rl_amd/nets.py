@@ -210,6 +210,7 @@ class MlpNet:
     def rows(self, epi, x, n, ep_t=None, timestep_limit=1.0, inv_n_global=1.0, act=None, adv=None, oldprob=None,
              target=None, out=None, ghead=None, partial=None, theta=None, image=None, tangent=None, image_t=None,
              skip=None, kl_coeff=0.0, kl_cutoff=0.0, cutoff_coeff=0.0, reverse_kl=0, feat_out=None):
+        self._check_time_feature(ep_t)
         own = (theta is None or theta is self.theta) and (image is None or image is self.image)
         theta = self.theta if theta is None else theta
         image = self.image if image is None else image
@@ -244,6 +245,11 @@ class MlpNet:
         call("mrl_mlp_rows" + self._sfx, ctypes.byref(self.desc), int(epi), ptr(theta), ptr(image), ptr(tangent),
              ptr(image_t), ctypes.byref(io), ptr(skip), stream())
 
+    def _check_time_feature(self, ep_t):
+        """A time feature built from ep_t sits beside n_in - 1 observation columns: at least one."""
+        if ep_t is not None and self.n_in < 2:
+            raise MrlError(f"a time-feature net (ep_t) needs n_in >= 2 (got n_in={self.n_in}: n_obs = 0)")
+
     def _key(self, x, n, ep_t, timestep_limit):
         return (self.theta.data_ptr(), self.theta._version, x.data_ptr(), int(n),
                 None if ep_t is None else ep_t.data_ptr(), float(timestep_limit))
@@ -267,6 +273,7 @@ class MlpNet:
         """out[P] (fp32) <- sum_n J_n^T ghead_n (per-wave slab + deterministic reduce); the
         forward comes from the activation cache when the last recording pass was at
         self.theta on the same rows."""
+        self._check_time_feature(ep_t)
         fn = self.lib.mrl_mlp_slab_rows_bf16 if self.bf16 else self.lib.mrl_mlp_slab_rows
         rows = int(fn(ctypes.byref(self.desc), int(n)))
         slab = self.ws.get("slab", rows * self.P, torch.float32)
