@@ -11,6 +11,7 @@
 #include "envs.h"
 #include "envs_chains.h"
 #include "envs_classic.h"
+#include "envs_planar.h"
 #include "mlp_device.h"
 
 namespace mrl {
@@ -206,6 +207,46 @@ struct EnvC<MRL_ENV_INVDOUBLEPENDULUM> {
   }
 };
 
+// the planar chains without contact (envs_planar.h): a thread steps an env whole, like Pendulum
+template <>
+struct EnvC<MRL_ENV_REACHER> {
+  static constexpr int NS = RC_NS, OBS = RC_OBS, ACT = RC_ACT, DISCRETE = 0, MAX_STEPS = RC_MAX_STEPS, NU = RC_NU,
+                       OBS_SLOTS = 0;
+  __device__ static void reset(const double* u, double* s) { reacher_reset(u, s); }
+  __device__ static void obs(const double* s, double* o) { reacher_obs(s, o); }
+  __device__ static void step_disc(double*, int, double&, bool&) {}
+  __device__ static void step_cont(double* s, const float* a, double& rew, bool& done) { reacher_step(s, a, rew, done); }
+  __device__ static void step_cont_quad(double* s, const float* a, double& rew, bool& done, int, const double*) {
+    reacher_step(s, a, rew, done);
+  }
+  template <class Out>
+  __device__ static void obs_out(const double* s, Out out) {
+    double o[OBS];
+    reacher_obs(s, o);
+#pragma unroll
+    for (int k = 0; k < OBS; ++k) out(k, o[k]);
+  }
+};
+template <>
+struct EnvC<MRL_ENV_SWIMMER> {
+  static constexpr int NS = SW_NS, OBS = SW_OBS, ACT = SW_ACT, DISCRETE = 0, MAX_STEPS = SW_MAX_STEPS, NU = SW_NU,
+                       OBS_SLOTS = 0;
+  __device__ static void reset(const double* u, double* s) { swimmer_reset(u, s); }
+  __device__ static void obs(const double* s, double* o) { swimmer_obs(s, o); }
+  __device__ static void step_disc(double*, int, double&, bool&) {}
+  __device__ static void step_cont(double* s, const float* a, double& rew, bool& done) { swimmer_step(s, a, rew, done); }
+  __device__ static void step_cont_quad(double* s, const float* a, double& rew, bool& done, int, const double*) {
+    swimmer_step(s, a, rew, done);
+  }
+  template <class Out>
+  __device__ static void obs_out(const double* s, Out out) {
+    double o[OBS];
+    swimmer_obs(s, o);
+#pragma unroll
+    for (int k = 0; k < OBS; ++k) out(k, o[k]);
+  }
+};
+
 struct EnvInfo {
   int ns, obs, act, discrete, max_steps;
 };
@@ -217,13 +258,15 @@ __host__ __device__ inline EnvInfo env_info(int id) {
   if (id == MRL_ENV_ACROBOT) return EnvInfo{AC_NS, AC_OBS, 3, 1, 500};
   if (id == MRL_ENV_INVPENDULUM) return EnvInfo{IP_NS, IP_OBS, IP_ACT, 0, 1000};
   if (id == MRL_ENV_INVDOUBLEPENDULUM) return EnvInfo{DP_NS, DP_OBS, DP_ACT, 0, 1000};
+  if (id == MRL_ENV_REACHER) return EnvInfo{RC_NS, RC_OBS, RC_ACT, 0, RC_MAX_STEPS};
+  if (id == MRL_ENV_SWIMMER) return EnvInfo{SW_NS, SW_OBS, SW_ACT, 0, SW_MAX_STEPS};
   return EnvInfo{HP_NS, HP_OBS, HP_ACT, 0, 1000};
 }
-// the ids the entry points take (MRL_ENV_*; 3 and 7 are not)
+// the ids the entry points take (MRL_ENV_*; 3, 7 and 10 are not)
 __host__ __device__ inline bool env_known(int id) {
   return id == MRL_ENV_CARTPOLE || id == MRL_ENV_HOPPER || id == MRL_ENV_HUMANOID || id == MRL_ENV_PENDULUM ||
          id == MRL_ENV_MOUNTAINCAR || id == MRL_ENV_ACROBOT || id == MRL_ENV_INVPENDULUM ||
-         id == MRL_ENV_INVDOUBLEPENDULUM;
+         id == MRL_ENV_INVDOUBLEPENDULUM || id == MRL_ENV_REACHER || id == MRL_ENV_SWIMMER;
 }
 __host__ __device__ inline int filt_doubles(int obs) { return 2 + 2 * (obs + 1); }
 

@@ -68,6 +68,8 @@ inline int check_fused_run(const mrl_rollout_desc* d, const mrl_mlp_desc* pol, c
       hipLaunchKernelGGL(KERNEL<MRL_ENV_INVPENDULUM>, __VA_ARGS__);                               \
     else if ((id) == MRL_ENV_INVDOUBLEPENDULUM)                                                   \
       hipLaunchKernelGGL(KERNEL<MRL_ENV_INVDOUBLEPENDULUM>, __VA_ARGS__);                         \
+    else if ((id) == MRL_ENV_REACHER) hipLaunchKernelGGL(KERNEL<MRL_ENV_REACHER>, __VA_ARGS__);    \
+    else if ((id) == MRL_ENV_SWIMMER) hipLaunchKernelGGL(KERNEL<MRL_ENV_SWIMMER>, __VA_ARGS__);    \
     else hipLaunchKernelGGL(KERNEL<MRL_ENV_HUMANOID>, __VA_ARGS__);                               \
   } while (0)
 
@@ -81,6 +83,8 @@ inline void dispatch_thread_env(int id, F&& f) {
   else if (id == MRL_ENV_ACROBOT) f(std::integral_constant<int, MRL_ENV_ACROBOT>{});
   else if (id == MRL_ENV_INVPENDULUM) f(std::integral_constant<int, MRL_ENV_INVPENDULUM>{});
   else if (id == MRL_ENV_INVDOUBLEPENDULUM) f(std::integral_constant<int, MRL_ENV_INVDOUBLEPENDULUM>{});
+  else if (id == MRL_ENV_REACHER) f(std::integral_constant<int, MRL_ENV_REACHER>{});
+  else if (id == MRL_ENV_SWIMMER) f(std::integral_constant<int, MRL_ENV_SWIMMER>{});
   else f(std::integral_constant<int, MRL_ENV_HOPPER>{});
 }
 #define MRL_DISPATCH_THREAD_ENV(id, KERNEL, ...) \

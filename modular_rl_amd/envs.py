@@ -1,6 +1,6 @@
 """Env registry for the device env steppers (replaces ``gym.envs.make``, run_pg.py:85).
 
-The dynamics live in ``csrc/envs.h`` / ``csrc/envs_classic.h`` / ``csrc/envs_chains.h`` / ``csrc/humanoid.h`` and run inside the rollout
+The dynamics live in ``csrc/envs.h`` / ``csrc/envs_classic.h`` / ``csrc/envs_chains.h`` / ``csrc/envs_planar.h`` / ``csrc/humanoid.h`` and run inside the rollout
 kernels; this module describes them with gym-compatible spaces / spec so that
 ``TrpoAgent(env.observation_space, env.action_space, cfg)`` and
 ``env.spec.max_episode_steps`` (run_pg.py:103-108) work unchanged, and ``VecEnv`` steps
@@ -18,6 +18,10 @@ them with the caller's own actions (``mrl_env_reset`` / ``mrl_env_step``).
   2- / 3-dof rigid-body chains (``csrc/envs_chains.h``: RK4, penalty joint limits): obs 4 / 11,
   one slider force in [-3, 3] / [-1, 1], TimeLimit 1000; done at |angle| > 0.2 / tip height <= 1.
   MuJoCo is not available, so their dynamics are a stand-in like Hopper's.
+* ``Reacher-v2``, ``Swimmer-v2`` -- gym's planar chains without contact (``csrc/envs_planar.h``):
+  a two-link arm with a goal drawn at reset and kept in the env state (obs 11, two torques in
+  [-1, 1], TimeLimit 50, never done by itself), and a free-floating three-link chain in a fluid
+  (obs 8, two torques in [-1, 1], TimeLimit 1000, never done by itself); stand-ins like the above.
 """
 import ctypes
 
@@ -65,6 +69,10 @@ REGISTRY = {
                                 obs_high=np.inf, act_high=3.0),
     "InvertedDoublePendulum-v2": dict(kind=_lib.ENV_INVDOUBLEPENDULUM, obs=11, act=1, discrete=False, max_steps=1000,
                                       obs_high=np.inf, act_high=1.0),
+    "Reacher-v2": dict(kind=_lib.ENV_REACHER, obs=11, act=2, discrete=False, max_steps=50, obs_high=np.inf,
+                       act_high=1.0),
+    "Swimmer-v2": dict(kind=_lib.ENV_SWIMMER, obs=8, act=2, discrete=False, max_steps=1000, obs_high=np.inf,
+                       act_high=1.0),
 }
 
 
