@@ -439,6 +439,8 @@ int64_t mrl_episode_stats_workspace_bytes(int64_t E);
 /* 10 is not an env */
 #define MRL_ENV_SWIMMER 11  /* Swimmer-v2: free-floating three-link chain in a fluid, obs 8, two torques in [-1, 1], TimeLimit 1000 */
 #define MRL_ENV_REACHER 12  /* Reacher-v2: two-link planar arm and a goal, obs 11, two torques in [-1, 1], TimeLimit 50 */
+/* 13 is not an env */
+#define MRL_ENV_HALFCHEETAH 14  /* HalfCheetah-v2: planar tree of seven bodies with ground contact, obs 17, six torques in [-1, 1], TimeLimit 1000 */
 
 typedef struct {
   int32_t env_id;          /* MRL_ENV_*                                          */
@@ -546,8 +548,8 @@ int mrl_rollout_finish(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, voi
  * bufs env_state and env_int only -- a Collector's envs and a stand-alone handle are the
  * same object.  Observations are the raw fp64 rows; mrl_obfilter_update_apply is the
  * ZFilter over them.  Every MRL_ENV_* id is served: CartPole, Hopper, Pendulum, MountainCar,
- * Acrobot, InvertedPendulum, InvertedDoublePendulum, Reacher and Swimmer by a thread per env,
- * Humanoid by a wave per env. */
+ * Acrobot, InvertedPendulum, InvertedDoublePendulum, Reacher, Swimmer and HalfCheetah by a thread
+ * per env, Humanoid by a wave per env. */
 typedef struct {
   const void* act;       /* step: [E] int32 (discrete) | [E, act_dim] float            */
   const uint8_t* mask;   /* reset: NULL = every env, else [E], non-zero = reset        */
@@ -608,8 +610,8 @@ typedef struct {
  * mrl_obfilter_update_apply(update = 0, clip = 5) gives; NULL or n_obs < 2: the raw
  * observation, clipped only.  From the desc: env_id, n_envs, timestep_limit, env_offset, seed;
  * from the bufs: env_state, env_int.  Every env but Humanoid (CartPole, Hopper, Pendulum,
- * MountainCar, Acrobot, InvertedPendulum, InvertedDoublePendulum, Reacher, Swimmer) with its
- * 64-64 policy net;
+ * MountainCar, Acrobot, InvertedPendulum, InvertedDoublePendulum, Reacher, Swimmer, HalfCheetah)
+ * with its 64-64 policy net;
  * anything else is MRL_E_UNSUPPORTED here -- smaller nets (the reference's CEM battery runs
  * hid_sizes 10,5) go through mrl_pop_rollout_mlp below. */
 int mrl_pop_rollout(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, const mrl_mlp_desc* pol,

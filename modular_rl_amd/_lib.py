@@ -22,6 +22,7 @@ ENV_CARTPOLE, ENV_HOPPER, ENV_HUMANOID = 0, 1, 2
 ENV_PENDULUM, ENV_MOUNTAINCAR, ENV_ACROBOT = 4, 5, 6  # 3 is not an env
 ENV_INVPENDULUM, ENV_INVDOUBLEPENDULUM = 8, 9  # 7 is not an env
 ENV_SWIMMER, ENV_REACHER = 11, 12  # 10 is not an env
+ENV_HALFCHEETAH = 14  # 13 is not an env
 GEMM_STORE, GEMM_TANH, GEMM_DTANH, GEMM_SLAB = 0, 1, 2, 3
 COMPUTE_F32, COMPUTE_BF16, COMPUTE_SPLIT = 0, 1, 2
 COMPUTE = {"fp32": COMPUTE_F32, "bf16": COMPUTE_BF16}

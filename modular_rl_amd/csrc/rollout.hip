@@ -301,9 +301,17 @@ __device__ inline void block_moments(const double* vals, int nvalid, int D, int 
   m2 = sum16(m);
 }
 
+// The 16 thread groups take columns K0 .. K0 + 15.  An env with more than COLS columns
+// (HalfCheetah: 17 obs + the reward) makes a second pass with K0 = COLS, whose first groups
+// take columns 16 .. D - 1 (the counts r[0], r[1] are column 0's, so the first pass's).
+// K0 is a template argument: as a function argument, even one that is 0 everywhere, it
+// changed the address arithmetic of every existing kernel.
+constexpr int COLS = RB / 16;
+constexpr int col_slots(int D) { return D > MAXD ? D : MAXD; }
+template <int K0 = 0>
 __device__ inline void publish_partial(const RollArgs& a, const double* vals, int nvalid, int D, bool with_rew,
                                        double* rec_out) {
-  const int k = threadIdx.x >> 4, j = threadIdx.x & 15;
+  const int k = K0 + (threadIdx.x >> 4), j = threadIdx.x & 15;
   double mean, m2;
   block_moments(vals, nvalid, D, k, j, mean, m2);
   if (k < D && j == 0) {
@@ -460,7 +468,8 @@ template <int ENV>
 __global__ __launch_bounds__(RB) void rollout_reset_kernel(RollArgs a) {
   using EC = EnvC<ENV>;
   constexpr int O = EC::OBS, D = O + 1;
-  __shared__ double vals[ENVS_PER_BLOCK * MAXD];
+  static_assert(D <= 2 * COLS, "two column passes");
+  __shared__ double vals[ENVS_PER_BLOCK * col_slots(D)];
   const int E = a.d.n_envs;
   const int le = threadIdx.x;
   const int e = blockIdx.x * ENVS_PER_BLOCK + le;
@@ -477,6 +486,7 @@ __global__ __launch_bounds__(RB) void rollout_reset_kernel(RollArgs a) {
   __syncthreads();
   const int nvalid = min(ENVS_PER_BLOCK, E - (int)blockIdx.x * ENVS_PER_BLOCK);
   publish_partial(a, vals, nvalid, D, false, a.b.records);
+  if constexpr (D > COLS) publish_partial<COLS>(a, vals, nvalid, D, false, a.b.records);
 }
 
 // rollout image: rimage_value (mlp_layout.h) of every element
@@ -523,8 +533,9 @@ __global__ __launch_bounds__(RB) void rollout_step_kernel(RollArgs a, const floa
                                                           const float* __restrict__ rimg, int t) {
   using EC = EnvC<ENV>;
   constexpr int O = EC::OBS, D = O + 1, NS = EC::NS, A = EC::ACT;
-  __shared__ double vals[ENVS_PER_BLOCK * MAXD];
-  __shared__ double fmean[MAXD], fden[MAXD];
+  static_assert(D <= 2 * COLS, "two column passes");
+  __shared__ double vals[ENVS_PER_BLOCK * col_slots(D)];
+  __shared__ double fmean[col_slots(D)], fden[col_slots(D)];
   __shared__ float xt[4][16][MAX_IN + 1];  // +1: conflict-free column reads
   // diagnostic phase stamps (100 MHz realtime) of block 0 / thread 0 -- never set in production
 #define STAMP(k)                                                                    \
@@ -596,6 +607,26 @@ __global__ __launch_bounds__(RB) void rollout_step_kernel(RollArgs a, const floa
       fden[k] = sqrt(var) + 1e-8;
     }
   }
+  if constexpr (D > COLS) {  // the columns past the 16 thread groups: a second pass by the first groups
+    const int k2 = k + COLS;
+    if (k2 < D) {
+      const bool isr2 = (k2 == O);
+      double fn2 = fs_in[isr2 ? 1 : 0], fM2 = fs_in[2 + k2], fS2 = fs_in[2 + D + k2];
+      double bn, bm, bs;
+      batch_of_records(rec_in, a.nb, a.RS, D, O, k2, jj, bn, bm, bs);
+      chan_merge(fn2, fM2, fS2, bn, bm, bs);
+      if (jj == 0 && blockIdx.x == 0) {
+        if (isr2) fs_out[1] = fn2;
+        fs_out[2 + k2] = fM2;
+        fs_out[2 + D + k2] = fS2;
+      }
+      if (!isr2 && jj == 0) {
+        const double var = fn2 > 1.0 ? fS2 / (fn2 - 1.0) : fM2 * fM2;
+        fmean[k2] = fM2;
+        fden[k2] = sqrt(var) + 1e-8;
+      }
+    }
+  }
   __syncthreads();
   STAMP(2);
 
@@ -644,6 +675,7 @@ __global__ __launch_bounds__(RB) void rollout_step_kernel(RollArgs a, const floa
   STAMP(6);
   const int nvalid = min(ENVS_PER_BLOCK, E - (int)blockIdx.x * ENVS_PER_BLOCK);
   publish_partial(a, vals, nvalid, D, true, rec_out);
+  if constexpr (D > COLS) publish_partial<COLS>(a, vals, nvalid, D, true, rec_out);
   STAMP(7);
   if (a.b.stamps != nullptr && blockIdx.x == 0 && threadIdx.x == 0)
     a.b.stamps[(int64_t)t * 16 + 15] = (int64_t)__builtin_amdgcn_s_memtime();
@@ -702,8 +734,10 @@ __device__ inline bool g_tag_is(gran_t g, int step) { return (g.w >> 31) == step
 
 // the block's (mean, M2) partial of vals[nvalid][D] (publish_partial's arithmetic) as
 // the granules of gather step `step`; lane 0 of column group k writes column k's
+// (K0: publish_partial's column pass)
+template <int K0 = 0>
 __device__ inline void publish_granules(const Granules& gr, const double* vals, int nvalid, int step) {
-  const int k = threadIdx.x >> 4, j = threadIdx.x & 15;
+  const int k = K0 + (threadIdx.x >> 4), j = threadIdx.x & 15;
   double mean, m2;
   block_moments(vals, nvalid, gr.D, k, j, mean, m2);
   if (k < gr.D && j == 0) gr.put(step, k, blockIdx.x, mean, m2);
@@ -771,8 +805,9 @@ __global__ __launch_bounds__(RB) void rollout_persistent_kernel(RollArgs a, cons
                                                                 uint32_t* __restrict__ sync) {
   using EC = EnvC<ENV>;
   constexpr int O = EC::OBS, D = O + 1, NS = EC::NS, A = EC::ACT;
-  __shared__ double vals[ENVS_PER_BLOCK * MAXD];
-  __shared__ double fmean[MAXD], fden[MAXD];
+  static_assert(D <= 2 * COLS, "two column passes");
+  __shared__ double vals[ENVS_PER_BLOCK * col_slots(D)];
+  __shared__ double fmean[col_slots(D)], fden[col_slots(D)];
   __shared__ float xt[4][16][MAX_IN + 1];  // +1: conflict-free column reads
   __shared__ int s_fail;
   // HP_CAP: the capsule constants, one LDS read per constant per substep instead of a
@@ -818,6 +853,17 @@ __global__ __launch_bounds__(RB) void rollout_persistent_kernel(RollArgs a, cons
     fM = a.b.filter_state[2 + k];
     fS = a.b.filter_state[2 + D + k];
   }
+  // the columns past the 16 thread groups (D > COLS): a second pass by the first groups
+  const int k2 = k + COLS;
+  const bool kcol2 = D > COLS && k2 < D, isr2 = (k2 == O);
+  double fn2 = 0.0, fM2 = 0.0, fS2 = 0.0;
+  if constexpr (D > COLS) {
+    if (kcol2) {
+      fn2 = a.b.filter_state[isr2 ? 1 : 0];
+      fM2 = a.b.filter_state[2 + k2];
+      fS2 = a.b.filter_state[2 + D + k2];
+    }
+  }
   // reset every env (core.py:186); all four rows of a wave hold the same env.  sn is
   // the start state of the env's NEXT episode, drawn ahead so an auto-reset is a copy:
   // its Philox draw runs behind the step's publish, under the hand-off latency.
@@ -837,6 +883,7 @@ __global__ __launch_bounds__(RB) void rollout_persistent_kernel(RollArgs a, cons
   }
   __syncthreads();
   publish_granules(gr, vals, nvalid, 0);  // gather step 0's partials
+  if constexpr (D > COLS) publish_granules<COLS>(gr, vals, nvalid, 0);
   double capr[6];  // row g's capsule constants
 #pragma unroll
   for (int f = 0; f < 6; ++f) capr[f] = hp_cap[4 * f + g];
@@ -889,6 +936,37 @@ __global__ __launch_bounds__(RB) void rollout_persistent_kernel(RollArgs a, cons
         const double var = fn > 1.0 ? fS / (fn - 1.0) : fM * fM;  // running_stat.py:27
         fmean[k] = fM;
         fden[k] = sqrt(var) + 1e-8;
+      }
+    }
+    if constexpr (D > COLS) {
+      // kcol2 is uniform in a 16-lane group, not in a wave (it holds for half of wave 0), and so
+      // is kcol where D is no multiple of 4: everything below works per 16-lane group
+      if (kcol2) {
+        double bn, bm, bs;
+        RecRound rr;
+        bool ok = true;
+        if (nb <= 16 * RB_MAX) {
+          ok = gather_granules(gr, rr, t, k2, jj, 0, E, t > 0, sync, refill_next);
+          rr.batch(bn, bm, bs);
+        } else {
+          double n = 0.0, sm = 0.0, raw = 0.0;
+          for (int b0 = 0; b0 < nb && ok; b0 += 16 * RB_MAX) {
+            ok = gather_granules(gr, rr, t, k2, jj, b0, E, t > 0, sync, refill_next);
+            rr.accumulate(n, sm, raw);
+          }
+          n = sum16(n);
+          sm = sum16(sm);
+          bm = n > 0.0 ? div_count(sm, n) : 0.0;
+          bn = n;
+          bs = sum16(raw) - n * bm * bm;
+        }
+        if (!ok) s_fail = 1;
+        chan_merge(fn2, fM2, fS2, bn, bm, bs);
+        if (!isr2 && jj == 0) {
+          const double var = fn2 > 1.0 ? fS2 / (fn2 - 1.0) : fM2 * fM2;
+          fmean[k2] = fM2;
+          fden[k2] = sqrt(var) + 1e-8;
+        }
       }
     }
     PSTAMP(t, 8);
@@ -954,6 +1032,10 @@ __global__ __launch_bounds__(RB) void rollout_persistent_kernel(RollArgs a, cons
     PSTAMP(t, 5);
     if (t + 1 < T) publish_granules(gr, vals, nvalid, t + 1);
     else publish_partial(a, vals, nvalid, D, true, a.b.records + (int64_t)(T & 1) * nb * a.RS);  // for finish
+    if constexpr (D > COLS) {
+      if (t + 1 < T) publish_granules<COLS>(gr, vals, nvalid, t + 1);
+      else publish_partial<COLS>(a, vals, nvalid, D, true, a.b.records + (int64_t)(T & 1) * nb * a.RS);
+    }
     PSTAMP(t, 6);
   }
 #undef PSTAMP
@@ -971,6 +1053,14 @@ __global__ __launch_bounds__(RB) void rollout_persistent_kernel(RollArgs a, cons
     if (isr) fs_out[1] = fn;
     fs_out[2 + k] = fM;
     fs_out[2 + D + k] = fS;
+  }
+  if constexpr (D > COLS) {
+    if (blockIdx.x == 0 && kcol2 && jj == 0) {
+      double* fs_out = a.b.filter_state + (T & 1) * a.FS;
+      if (isr2) fs_out[1] = fn2;
+      fs_out[2 + k2] = fM2;
+      fs_out[2 + D + k2] = fS2;
+    }
   }
 }
 

@@ -12,6 +12,7 @@
 #include "envs_chains.h"
 #include "envs_classic.h"
 #include "envs_planar.h"
+#include "envs_tree.h"
 #include "mlp_device.h"
 
 namespace mrl {
@@ -247,6 +248,30 @@ struct EnvC<MRL_ENV_SWIMMER> {
   }
 };
 
+// the planar tree with ground contact (envs_tree.h): a thread steps an env whole, so the four
+// rows of the fused step all step it identically, as Reacher's do
+template <>
+struct EnvC<MRL_ENV_HALFCHEETAH> {
+  static constexpr int NS = HC_NS, OBS = HC_OBS, ACT = HC_ACT, DISCRETE = 0, MAX_STEPS = HC_MAX_STEPS, NU = HC_NU,
+                       OBS_SLOTS = 0;
+  __device__ static void reset(const double* u, double* s) { halfcheetah_reset(u, s); }
+  __device__ static void obs(const double* s, double* o) { halfcheetah_obs(s, o); }
+  __device__ static void step_disc(double*, int, double&, bool&) {}
+  __device__ static void step_cont(double* s, const float* a, double& rew, bool& done) {
+    halfcheetah_step(s, a, rew, done);
+  }
+  __device__ static void step_cont_quad(double* s, const float* a, double& rew, bool& done, int, const double*) {
+    halfcheetah_step(s, a, rew, done);
+  }
+  template <class Out>
+  __device__ static void obs_out(const double* s, Out out) {
+    double o[OBS];
+    halfcheetah_obs(s, o);
+#pragma unroll
+    for (int k = 0; k < OBS; ++k) out(k, o[k]);
+  }
+};
+
 struct EnvInfo {
   int ns, obs, act, discrete, max_steps;
 };
@@ -260,13 +285,15 @@ __host__ __device__ inline EnvInfo env_info(int id) {
   if (id == MRL_ENV_INVDOUBLEPENDULUM) return EnvInfo{DP_NS, DP_OBS, DP_ACT, 0, 1000};
   if (id == MRL_ENV_REACHER) return EnvInfo{RC_NS, RC_OBS, RC_ACT, 0, RC_MAX_STEPS};
   if (id == MRL_ENV_SWIMMER) return EnvInfo{SW_NS, SW_OBS, SW_ACT, 0, SW_MAX_STEPS};
+  if (id == MRL_ENV_HALFCHEETAH) return EnvInfo{HC_NS, HC_OBS, HC_ACT, 0, HC_MAX_STEPS};
   return EnvInfo{HP_NS, HP_OBS, HP_ACT, 0, 1000};
 }
-// the ids the entry points take (MRL_ENV_*; 3, 7 and 10 are not)
+// the ids the entry points take (MRL_ENV_*; 3, 7, 10 and 13 are not)
 __host__ __device__ inline bool env_known(int id) {
   return id == MRL_ENV_CARTPOLE || id == MRL_ENV_HOPPER || id == MRL_ENV_HUMANOID || id == MRL_ENV_PENDULUM ||
          id == MRL_ENV_MOUNTAINCAR || id == MRL_ENV_ACROBOT || id == MRL_ENV_INVPENDULUM ||
-         id == MRL_ENV_INVDOUBLEPENDULUM || id == MRL_ENV_REACHER || id == MRL_ENV_SWIMMER;
+         id == MRL_ENV_INVDOUBLEPENDULUM || id == MRL_ENV_REACHER || id == MRL_ENV_SWIMMER ||
+         id == MRL_ENV_HALFCHEETAH;
 }
 __host__ __device__ inline int filt_doubles(int obs) { return 2 + 2 * (obs + 1); }
 

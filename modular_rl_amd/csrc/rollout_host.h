@@ -70,6 +70,8 @@ inline int check_fused_run(const mrl_rollout_desc* d, const mrl_mlp_desc* pol, c
       hipLaunchKernelGGL(KERNEL<MRL_ENV_INVDOUBLEPENDULUM>, __VA_ARGS__);                         \
     else if ((id) == MRL_ENV_REACHER) hipLaunchKernelGGL(KERNEL<MRL_ENV_REACHER>, __VA_ARGS__);    \
     else if ((id) == MRL_ENV_SWIMMER) hipLaunchKernelGGL(KERNEL<MRL_ENV_SWIMMER>, __VA_ARGS__);    \
+    else if ((id) == MRL_ENV_HALFCHEETAH)                                                         \
+      hipLaunchKernelGGL(KERNEL<MRL_ENV_HALFCHEETAH>, __VA_ARGS__);                               \
     else hipLaunchKernelGGL(KERNEL<MRL_ENV_HUMANOID>, __VA_ARGS__);                               \
   } while (0)
 
@@ -85,6 +87,7 @@ inline void dispatch_thread_env(int id, F&& f) {
   else if (id == MRL_ENV_INVDOUBLEPENDULUM) f(std::integral_constant<int, MRL_ENV_INVDOUBLEPENDULUM>{});
   else if (id == MRL_ENV_REACHER) f(std::integral_constant<int, MRL_ENV_REACHER>{});
   else if (id == MRL_ENV_SWIMMER) f(std::integral_constant<int, MRL_ENV_SWIMMER>{});
+  else if (id == MRL_ENV_HALFCHEETAH) f(std::integral_constant<int, MRL_ENV_HALFCHEETAH>{});
   else f(std::integral_constant<int, MRL_ENV_HOPPER>{});
 }
 #define MRL_DISPATCH_THREAD_ENV(id, KERNEL, ...) \

@@ -1,6 +1,6 @@
 """Env registry for the device env steppers (replaces ``gym.envs.make``, run_pg.py:85).
 
-The dynamics live in ``csrc/envs.h`` / ``csrc/envs_classic.h`` / ``csrc/envs_chains.h`` / ``csrc/envs_planar.h`` / ``csrc/humanoid.h`` and run inside the rollout
+The dynamics live in ``csrc/envs.h`` / ``csrc/envs_classic.h`` / ``csrc/envs_chains.h`` / ``csrc/envs_planar.h`` / ``csrc/envs_tree.h`` / ``csrc/humanoid.h`` and run inside the rollout
 kernels; this module describes them with gym-compatible spaces / spec so that
 ``TrpoAgent(env.observation_space, env.action_space, cfg)`` and
 ``env.spec.max_episode_steps`` (run_pg.py:103-108) work unchanged, and ``VecEnv`` steps
@@ -22,6 +22,10 @@ them with the caller's own actions (``mrl_env_reset`` / ``mrl_env_step``).
   a two-link arm with a goal drawn at reset and kept in the env state (obs 11, two torques in
   [-1, 1], TimeLimit 50, never done by itself), and a free-floating three-link chain in a fluid
   (obs 8, two torques in [-1, 1], TimeLimit 1000, never done by itself); stand-ins like the above.
+* ``HalfCheetah-v2`` -- gym's planar tree of seven bodies, two legs on one torso, with Hopper's
+  compliant ground contact and passive joint springs (``csrc/envs_tree.h``: the dynamics over a
+  model table with a parent index per body): obs 17, six torques in [-1, 1], TimeLimit 1000,
+  never done by itself; a stand-in like the above.
 """
 import ctypes
 
@@ -73,6 +77,8 @@ REGISTRY = {
                        act_high=1.0),
     "Swimmer-v2": dict(kind=_lib.ENV_SWIMMER, obs=8, act=2, discrete=False, max_steps=1000, obs_high=np.inf,
                        act_high=1.0),
+    "HalfCheetah-v2": dict(kind=_lib.ENV_HALFCHEETAH, obs=17, act=6, discrete=False, max_steps=1000,
+                           obs_high=np.inf, act_high=1.0),
 }
 
 
