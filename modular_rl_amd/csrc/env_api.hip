@@ -40,12 +40,12 @@ __global__ __launch_bounds__(64) void env_step_kernel(RollArgs a, mrl_env_io io,
   double rew = 0.0;
   bool done = false;
   if constexpr (EC::DISCRETE) {
-    EC::step_disc(s, reinterpret_cast<const int32_t*>(io.act)[e], rew, done);
+    EC::step(s, reinterpret_cast<const int32_t*>(io.act)[e], rew, done);
   } else {
     float av[A];
 #pragma unroll
     for (int q = 0; q < A; ++q) av[q] = reinterpret_cast<const float*>(io.act)[(int64_t)e * A + q];
-    EC::step_cont(s, av, rew, done);
+    EC::step(s, av, rew, done);
   }
   const int ept = a.b.env_int[e];
   bool term, last;

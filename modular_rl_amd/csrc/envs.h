@@ -51,6 +51,13 @@ __device__ inline void cartpole_obs(const double* s, double* o) {
   for (int i = 0; i < 4; ++i) o[i] = s[i];
 }
 
+struct CartPoleEnv {
+  static constexpr int NS = CP_NS, OBS = CP_OBS, ACT = 2, DISCRETE = 1, MAX_STEPS = 200, NU = 4;
+  __device__ static void reset(const double* u, double* s) { cartpole_reset(u, s); }
+  __device__ static void obs(const double* s, double* o) { cartpole_obs(s, o); }
+  __device__ static void step(double* s, int a, double& rew, bool& done) { cartpole_step(s, a, rew, done); }
+};
+
 // ------------------------------------------------------------------ Hopper-v2
 // gym's hopper.xml as planar articulated rigid-body dynamics (oracle/envs.py has
 // the model, its constants and this exact operation order):
@@ -378,6 +385,13 @@ __device__ inline void hopper_obs(const double* s, double* o) {
   for (int i = 0; i < 5; ++i) o[i] = s[1 + i];
   for (int i = 0; i < 6; ++i) o[5 + i] = clampd(s[6 + i], -10.0, 10.0);
 }
+
+struct HopperEnv {
+  static constexpr int NS = HP_NS, OBS = HP_OBS, ACT = HP_ACT, DISCRETE = 0, MAX_STEPS = 1000, NU = 12;
+  __device__ static void reset(const double* u, double* s) { hopper_reset(u, s); }
+  __device__ static void obs(const double* s, double* o) { hopper_obs(s, o); }
+  __device__ static void step(double* s, const float* a, double& rew, bool& done) { hopper_step(s, a, rew, done); }
+};
 
 }  // namespace mrl
 

@@ -157,6 +157,13 @@ __device__ inline void invpendulum_obs(const double* s, double* o) {
   for (int i = 0; i < 4; ++i) o[i] = s[i];
 }
 
+struct InvPendulumEnv {
+  static constexpr int NS = IP_NS, OBS = IP_OBS, ACT = IP_ACT, DISCRETE = 0, MAX_STEPS = 1000, NU = IP_NU;
+  __device__ static void reset(const double* u, double* s) { invpendulum_reset(u, s); }
+  __device__ static void obs(const double* s, double* o) { invpendulum_obs(s, o); }
+  __device__ static void step(double* s, const float* a, double& rew, bool& done) { invpendulum_step(s, a, rew, done); }
+};
+
 // ------------------------------------------------------------------ InvertedDoublePendulum-v2
 constexpr int DP_NS = 6, DP_OBS = 11, DP_ACT = 1, DP_NU = 8, DP_FRAME_SKIP = 5;
 constexpr double DP_DT = 0.01, DP_GEAR = 500.0, DP_CTRL = 1.0, DP_DAMP = 0.05, DP_GX = 1e-5, DP_GZ = -9.81;
@@ -246,5 +253,14 @@ __device__ inline void invdoublependulum_obs(const double* s, double* o) {
   o[9] = 0.0;
   o[10] = 0.0;
 }
+
+struct InvDoublePendulumEnv {
+  static constexpr int NS = DP_NS, OBS = DP_OBS, ACT = DP_ACT, DISCRETE = 0, MAX_STEPS = 1000, NU = DP_NU;
+  __device__ static void reset(const double* u, double* s) { invdoublependulum_reset(u, s); }
+  __device__ static void obs(const double* s, double* o) { invdoublependulum_obs(s, o); }
+  __device__ static void step(double* s, const float* a, double& rew, bool& done) {
+    invdoublependulum_step(s, a, rew, done);
+  }
+};
 
 }  // namespace mrl

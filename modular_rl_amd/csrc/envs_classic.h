@@ -53,6 +53,13 @@ __device__ inline void pendulum_obs(const double* s, double* o) {
   o[2] = s[1];
 }
 
+struct PendulumEnv {
+  static constexpr int NS = PD_NS, OBS = PD_OBS, ACT = PD_ACT, DISCRETE = 0, MAX_STEPS = 200, NU = 2;
+  __device__ static void reset(const double* u, double* s) { pendulum_reset(u, s); }
+  __device__ static void obs(const double* s, double* o) { pendulum_obs(s, o); }
+  __device__ static void step(double* s, const float* a, double& rew, bool& done) { pendulum_step(s, a, rew, done); }
+};
+
 // ------------------------------------------------------------------ MountainCar-v0
 constexpr int MC_NS = 2, MC_OBS = 2;
 constexpr double MC_MIN_POS = -1.2, MC_MAX_POS = 0.6, MC_MAX_SPEED = 0.07, MC_GOAL = 0.5;
@@ -79,6 +86,13 @@ __device__ inline void mountaincar_obs(const double* s, double* o) {
   o[0] = s[0];
   o[1] = s[1];
 }
+
+struct MountainCarEnv {
+  static constexpr int NS = MC_NS, OBS = MC_OBS, ACT = 3, DISCRETE = 1, MAX_STEPS = 200, NU = 2;
+  __device__ static void reset(const double* u, double* s) { mountaincar_reset(u, s); }
+  __device__ static void obs(const double* s, double* o) { mountaincar_obs(s, o); }
+  __device__ static void step(double* s, int a, double& rew, bool& done) { mountaincar_step(s, a, rew, done); }
+};
 
 // ------------------------------------------------------------------ Acrobot-v1
 constexpr int AC_NS = 4, AC_OBS = 6;
@@ -152,5 +166,12 @@ __device__ inline void acrobot_obs(const double* s, double* o) {
   o[4] = s[2];
   o[5] = s[3];
 }
+
+struct AcrobotEnv {
+  static constexpr int NS = AC_NS, OBS = AC_OBS, ACT = 3, DISCRETE = 1, MAX_STEPS = 500, NU = 4;
+  __device__ static void reset(const double* u, double* s) { acrobot_reset(u, s); }
+  __device__ static void obs(const double* s, double* o) { acrobot_obs(s, o); }
+  __device__ static void step(double* s, int a, double& rew, bool& done) { acrobot_step(s, a, rew, done); }
+};
 
 }  // namespace mrl

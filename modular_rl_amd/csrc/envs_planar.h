@@ -181,6 +181,13 @@ __device__ inline void reacher_obs(const double* s, double* o) {
   o[10] = 0.0;
 }
 
+struct ReacherEnv {
+  static constexpr int NS = RC_NS, OBS = RC_OBS, ACT = RC_ACT, DISCRETE = 0, MAX_STEPS = RC_MAX_STEPS, NU = RC_NU;
+  __device__ static void reset(const double* u, double* s) { reacher_reset(u, s); }
+  __device__ static void obs(const double* s, double* o) { reacher_obs(s, o); }
+  __device__ static void step(double* s, const float* a, double& rew, bool& done) { reacher_step(s, a, rew, done); }
+};
+
 // ------------------------------------------------------------------ Swimmer-v2
 constexpr int SW_NS = 10, SW_NQ = 5, SW_OBS = 8, SW_ACT = 2, SW_NU = 10, SW_FRAME_SKIP = 4, SW_MAX_STEPS = 1000;
 constexpr double SW_DT = 0.01, SW_GEAR = 150.0, SW_CTRL = 1.0, SW_ARM = 0.1;
@@ -330,5 +337,12 @@ __device__ inline void swimmer_step(double* s, const float* a, double& rew, bool
 __device__ inline void swimmer_obs(const double* s, double* o) {
   for (int i = 0; i < SW_OBS; ++i) o[i] = s[2 + i];
 }
+
+struct SwimmerEnv {
+  static constexpr int NS = SW_NS, OBS = SW_OBS, ACT = SW_ACT, DISCRETE = 0, MAX_STEPS = SW_MAX_STEPS, NU = SW_NU;
+  __device__ static void reset(const double* u, double* s) { swimmer_reset(u, s); }
+  __device__ static void obs(const double* s, double* o) { swimmer_obs(s, o); }
+  __device__ static void step(double* s, const float* a, double& rew, bool& done) { swimmer_step(s, a, rew, done); }
+};
 
 }  // namespace mrl

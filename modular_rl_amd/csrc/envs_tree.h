@@ -467,4 +467,11 @@ __device__ inline void halfcheetah_obs(const double* s, double* o) {
   for (int i = 0; i < HC_OBS; ++i) o[i] = s[1 + i];
 }
 
+struct HalfCheetahEnv {
+  static constexpr int NS = HC_NS, OBS = HC_OBS, ACT = HC_ACT, DISCRETE = 0, MAX_STEPS = HC_MAX_STEPS, NU = HC_NU;
+  __device__ static void reset(const double* u, double* s) { halfcheetah_reset(u, s); }
+  __device__ static void obs(const double* s, double* o) { halfcheetah_obs(s, o); }
+  __device__ static void step(double* s, const float* a, double& rew, bool& done) { halfcheetah_step(s, a, rew, done); }
+};
+
 }  // namespace mrl

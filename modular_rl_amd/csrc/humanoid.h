@@ -1090,5 +1090,9 @@ __device__ inline void observation(const Wave& W, const Shared& S, int lane, Out
 
 constexpr int HM_NQ = hm::NQ, HM_NV = hm::NV, HM_ACT = hm::NACT, HM_NS = hm::NS, HM_OBS = hm::OBS, HM_NU = hm::NU;
 constexpr int HM_KCACHE = hm::KCACHE;
+// stepped by the wave-per-env kernels (hm_*_kernel), not per thread: the constants only
+struct HumanoidEnv {
+  static constexpr int NS = HM_NS, OBS = HM_OBS, ACT = HM_ACT, DISCRETE = 0, MAX_STEPS = 1000, NU = HM_NU;
+};
 
 }  // namespace mrl

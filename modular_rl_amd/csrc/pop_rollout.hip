@@ -5,7 +5,7 @@
 // env e driven by theta row e under the deterministic policy (agentzoo.py:116-123).  One
 // launch runs every episode to its end.
 //
-// Layout: a lane per candidate, one wave per block.  The physics (step_cont / step_disc, the
+// Layout: a lane per candidate, one wave per block.  The physics (the envs' step, the
 // functions of env_step_kernel: the same bits) runs at full lane use; the policy forward is
 // 64 independent fmaf chains.  Every lane needs its OWN weights, row-major [N, P] in memory, so
 // lane-strided reads would touch 64 lines per load: instead the wave streams theta in chunks of
@@ -188,14 +188,14 @@ __global__ __launch_bounds__(POP_W) void pop_rollout_kernel(RollArgs a, PopArgs 
         for (int q = 1; q < A; ++q)
           if (z[q] > z[act]) act = q;
         if (t < p.io.trace_steps) reinterpret_cast<int32_t*>(p.io.trace_act)[(int64_t)t * N + e] = act;
-        EC::step_disc(s, act, rew, done);
+        EC::step(s, act, rew, done);
       } else {
         if (t < p.io.trace_steps) {
           float* arow = reinterpret_cast<float*>(p.io.trace_act) + ((int64_t)t * N + e) * A;
 #pragma unroll
           for (int q = 0; q < A; ++q) arow[q] = z[q];
         }
-        EC::step_cont(s, z, rew, done);
+        EC::step(s, z, rew, done);
       }
       if (t < p.io.trace_steps) p.io.trace_rew[(int64_t)t * N + e] = rew;
       ret += rew;

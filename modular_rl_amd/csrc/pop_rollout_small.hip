@@ -186,14 +186,14 @@ __global__ __launch_bounds__(PS_W) void pop_rollout_small_kernel(RollArgs a, Pop
         for (int q = 1; q < A; ++q)
           if (z[q] > z[act]) act = q;
         if (t < p.io.trace_steps) reinterpret_cast<int32_t*>(p.io.trace_act)[(int64_t)t * N + e] = act;
-        EC::step_disc(s, act, rew, done);
+        EC::step(s, act, rew, done);
       } else {
         if (t < p.io.trace_steps) {
           float* arow = reinterpret_cast<float*>(p.io.trace_act) + ((int64_t)t * N + e) * A;
 #pragma unroll
           for (int q = 0; q < A; ++q) arow[q] = z[q];
         }
-        EC::step_cont(s, z, rew, done);
+        EC::step(s, z, rew, done);
       }
       if (t < p.io.trace_steps) p.io.trace_rew[(int64_t)t * N + e] = rew;
       ret += rew;

@@ -1,11 +1,15 @@
 // Device code shared by the rollout units -- rollout.hip (the fused 64-64 path),
 // rollout_layered.hip (the layered path), env_api.hip (the stand-alone env stepper and obs
-// filter) and cem.hip (the population rollout): the env traits EnvC<> and the launch arguments
-// RollArgs, env reset / sampling noise / sample-and-step / episode bookkeeping, the 16-lane
-// fp64 sums, the Chan merge, the layered path's column partial and record merge, and the
-// block set-up of the Humanoid wave-per-env kernels.
+// filter) and pop_rollout*.hip (the population rollouts): the list of the device envs
+// (MRL_ENV_LIST) with what is generated from it -- EnvC<>, env_info(), env_known() -- the launch
+// arguments RollArgs, env reset / sampling noise / sample-and-step / episode bookkeeping, the
+// 16-lane fp64 sums, the Chan merge, the layered path's column partial and record merge, and
+// the block set-up of the Humanoid wave-per-env kernels.  An env's dynamics and its traits
+// struct are in its own header (envs*.h, humanoid.h).
 #pragma once
 #include <math.h>
+
+#include <type_traits>
 
 #include "../../include/mrl_hip.h"
 #include "envs.h"
@@ -62,238 +66,75 @@ struct HopperQuad {
   }
 };
 
-template <int ENV>
-struct EnvC;
-template <>
-struct EnvC<MRL_ENV_CARTPOLE> {
-  static constexpr int NS = CP_NS, OBS = CP_OBS, ACT = 2, DISCRETE = 1, MAX_STEPS = 200, NU = 4, OBS_SLOTS = 0;
-  __device__ static void reset(const double* u, double* s) { cartpole_reset(u, s); }
-  __device__ static void obs(const double* s, double* o) { cartpole_obs(s, o); }
-  __device__ static void step_disc(double* s, int a, double& rew, bool& done) { cartpole_step(s, a, rew, done); }
-  __device__ static void step_cont(double*, const float*, double&, bool&) {}
-  __device__ static void step_cont_quad(double*, const float*, double&, bool&, int, const double*) {}
-  template <class Out>
-  __device__ static void obs_out(const double* s, Out out) {
-    double o[OBS];
-    cartpole_obs(s, o);
-#pragma unroll
-    for (int k = 0; k < OBS; ++k) out(k, o[k]);
-  }
-};
-template <>
-struct EnvC<MRL_ENV_HOPPER> {
-  static constexpr int NS = HP_NS, OBS = HP_OBS, ACT = HP_ACT, DISCRETE = 0, MAX_STEPS = 1000, NU = 12,
-                       OBS_SLOTS = 0;
-  __device__ static void reset(const double* u, double* s) { hopper_reset(u, s); }
-  __device__ static void obs(const double* s, double* o) { hopper_obs(s, o); }
-  __device__ static void step_disc(double*, int, double&, bool&) {}
-  __device__ static void step_cont(double* s, const float* a, double& rew, bool& done) { hopper_step(s, a, rew, done); }
+// One line per device env: the MRL_ENV_* id (include/mrl_hip.h) and the traits struct its
+// header declares beside its dynamics -- constants NS / OBS / ACT / DISCRETE / MAX_STEPS / NU,
+// reset(u, s), obs(s, o) and one step(s, a, rew, done) taking an int action (DISCRETE) or a
+// const float* one.  T: an env a thread steps whole; W: Humanoid, stepped by the wave-per-env
+// kernels (hm_*_kernel), constants only.  EnvC<>, env_info(), env_known() and rollout_host.h's
+// two dispatches are generated from this list and name no env themselves.
+#define MRL_ENV_LIST(T, W)                            \
+  T(MRL_ENV_CARTPOLE, CartPoleEnv)                    \
+  T(MRL_ENV_HOPPER, HopperEnv)                        \
+  T(MRL_ENV_PENDULUM, PendulumEnv)                    \
+  T(MRL_ENV_MOUNTAINCAR, MountainCarEnv)              \
+  T(MRL_ENV_ACROBOT, AcrobotEnv)                      \
+  T(MRL_ENV_INVPENDULUM, InvPendulumEnv)              \
+  T(MRL_ENV_INVDOUBLEPENDULUM, InvDoublePendulumEnv)  \
+  T(MRL_ENV_REACHER, ReacherEnv)                      \
+  T(MRL_ENV_SWIMMER, SwimmerEnv)                      \
+  T(MRL_ENV_HALFCHEETAH, HalfCheetahEnv)              \
+  W(MRL_ENV_HUMANOID, HumanoidEnv)
+#define MRL_ENV_NONE(ID, E)
+
+// What the kernels see of an env: its traits E, and over them the obs rows handed to `out`
+// and the fused step kernel's step.  A thread steps an env whole, so the four rows of the
+// fused step all step it identically; only Hopper splits the work over them (HopperQuad).
+template <class E>
+struct EnvAdaptor : E {
   __device__ static void step_cont_quad(double* s, const float* a, double& rew, bool& done, int g,
                                         const double* capc) {
-    hopper_step(s, a, rew, done, HopperQuad{g, capc});
+    if constexpr (std::is_same_v<E, HopperEnv>) hopper_step(s, a, rew, done, HopperQuad{g, capc});
+    else E::step(s, a, rew, done);
   }
   template <class Out>
   __device__ static void obs_out(const double* s, Out out) {
-    double o[OBS];
-    hopper_obs(s, o);
+    double o[E::OBS];
+    E::obs(s, o);
 #pragma unroll
-    for (int k = 0; k < OBS; ++k) out(k, o[k]);
+    for (int k = 0; k < E::OBS; ++k) out(k, o[k]);
   }
 };
-template <>
-struct EnvC<MRL_ENV_HUMANOID> {  // stepped by the wave-per-env kernels (hm_*_kernel), not per thread
-  static constexpr int NS = HM_NS, OBS = HM_OBS, ACT = HM_ACT, DISCRETE = 0, MAX_STEPS = 1000, NU = HM_NU,
-                       OBS_SLOTS = 0;
-  __device__ static void reset(const double*, double*) {}
-  __device__ static void step_disc(double*, int, double&, bool&) {}
-  __device__ static void step_cont(double*, const float*, double&, bool&) {}
-  template <class Out>
-  __device__ static void obs_out(const double*, Out) {}
-};
-
-// the classic-control envs (envs_classic.h): a thread steps an env whole, so the four rows
-// of the fused step all step it identically, as CartPole's do
-template <>
-struct EnvC<MRL_ENV_PENDULUM> {
-  static constexpr int NS = PD_NS, OBS = PD_OBS, ACT = PD_ACT, DISCRETE = 0, MAX_STEPS = 200, NU = 2, OBS_SLOTS = 0;
-  __device__ static void reset(const double* u, double* s) { pendulum_reset(u, s); }
-  __device__ static void obs(const double* s, double* o) { pendulum_obs(s, o); }
-  __device__ static void step_disc(double*, int, double&, bool&) {}
-  __device__ static void step_cont(double* s, const float* a, double& rew, bool& done) { pendulum_step(s, a, rew, done); }
-  __device__ static void step_cont_quad(double* s, const float* a, double& rew, bool& done, int, const double*) {
-    pendulum_step(s, a, rew, done);
-  }
-  template <class Out>
-  __device__ static void obs_out(const double* s, Out out) {
-    double o[OBS];
-    pendulum_obs(s, o);
-#pragma unroll
-    for (int k = 0; k < OBS; ++k) out(k, o[k]);
-  }
-};
-template <>
-struct EnvC<MRL_ENV_MOUNTAINCAR> {
-  static constexpr int NS = MC_NS, OBS = MC_OBS, ACT = 3, DISCRETE = 1, MAX_STEPS = 200, NU = 2, OBS_SLOTS = 0;
-  __device__ static void reset(const double* u, double* s) { mountaincar_reset(u, s); }
-  __device__ static void obs(const double* s, double* o) { mountaincar_obs(s, o); }
-  __device__ static void step_disc(double* s, int a, double& rew, bool& done) { mountaincar_step(s, a, rew, done); }
-  __device__ static void step_cont(double*, const float*, double&, bool&) {}
-  __device__ static void step_cont_quad(double*, const float*, double&, bool&, int, const double*) {}
-  template <class Out>
-  __device__ static void obs_out(const double* s, Out out) {
-    double o[OBS];
-    mountaincar_obs(s, o);
-#pragma unroll
-    for (int k = 0; k < OBS; ++k) out(k, o[k]);
-  }
-};
-template <>
-struct EnvC<MRL_ENV_ACROBOT> {
-  static constexpr int NS = AC_NS, OBS = AC_OBS, ACT = 3, DISCRETE = 1, MAX_STEPS = 500, NU = 4, OBS_SLOTS = 0;
-  __device__ static void reset(const double* u, double* s) { acrobot_reset(u, s); }
-  __device__ static void obs(const double* s, double* o) { acrobot_obs(s, o); }
-  __device__ static void step_disc(double* s, int a, double& rew, bool& done) { acrobot_step(s, a, rew, done); }
-  __device__ static void step_cont(double*, const float*, double&, bool&) {}
-  __device__ static void step_cont_quad(double*, const float*, double&, bool&, int, const double*) {}
-  template <class Out>
-  __device__ static void obs_out(const double* s, Out out) {
-    double o[OBS];
-    acrobot_obs(s, o);
-#pragma unroll
-    for (int k = 0; k < OBS; ++k) out(k, o[k]);
-  }
-};
-
-// the cart-and-pole chains (envs_chains.h): a thread steps an env whole, like Pendulum
-template <>
-struct EnvC<MRL_ENV_INVPENDULUM> {
-  static constexpr int NS = IP_NS, OBS = IP_OBS, ACT = IP_ACT, DISCRETE = 0, MAX_STEPS = 1000, NU = IP_NU,
-                       OBS_SLOTS = 0;
-  __device__ static void reset(const double* u, double* s) { invpendulum_reset(u, s); }
-  __device__ static void obs(const double* s, double* o) { invpendulum_obs(s, o); }
-  __device__ static void step_disc(double*, int, double&, bool&) {}
-  __device__ static void step_cont(double* s, const float* a, double& rew, bool& done) {
-    invpendulum_step(s, a, rew, done);
-  }
-  __device__ static void step_cont_quad(double* s, const float* a, double& rew, bool& done, int, const double*) {
-    invpendulum_step(s, a, rew, done);
-  }
-  template <class Out>
-  __device__ static void obs_out(const double* s, Out out) {
-    double o[OBS];
-    invpendulum_obs(s, o);
-#pragma unroll
-    for (int k = 0; k < OBS; ++k) out(k, o[k]);
-  }
-};
-template <>
-struct EnvC<MRL_ENV_INVDOUBLEPENDULUM> {
-  static constexpr int NS = DP_NS, OBS = DP_OBS, ACT = DP_ACT, DISCRETE = 0, MAX_STEPS = 1000, NU = DP_NU,
-                       OBS_SLOTS = 0;
-  __device__ static void reset(const double* u, double* s) { invdoublependulum_reset(u, s); }
-  __device__ static void obs(const double* s, double* o) { invdoublependulum_obs(s, o); }
-  __device__ static void step_disc(double*, int, double&, bool&) {}
-  __device__ static void step_cont(double* s, const float* a, double& rew, bool& done) {
-    invdoublependulum_step(s, a, rew, done);
-  }
-  __device__ static void step_cont_quad(double* s, const float* a, double& rew, bool& done, int, const double*) {
-    invdoublependulum_step(s, a, rew, done);
-  }
-  template <class Out>
-  __device__ static void obs_out(const double* s, Out out) {
-    double o[OBS];
-    invdoublependulum_obs(s, o);
-#pragma unroll
-    for (int k = 0; k < OBS; ++k) out(k, o[k]);
-  }
-};
-
-// the planar chains without contact (envs_planar.h): a thread steps an env whole, like Pendulum
-template <>
-struct EnvC<MRL_ENV_REACHER> {
-  static constexpr int NS = RC_NS, OBS = RC_OBS, ACT = RC_ACT, DISCRETE = 0, MAX_STEPS = RC_MAX_STEPS, NU = RC_NU,
-                       OBS_SLOTS = 0;
-  __device__ static void reset(const double* u, double* s) { reacher_reset(u, s); }
-  __device__ static void obs(const double* s, double* o) { reacher_obs(s, o); }
-  __device__ static void step_disc(double*, int, double&, bool&) {}
-  __device__ static void step_cont(double* s, const float* a, double& rew, bool& done) { reacher_step(s, a, rew, done); }
-  __device__ static void step_cont_quad(double* s, const float* a, double& rew, bool& done, int, const double*) {
-    reacher_step(s, a, rew, done);
-  }
-  template <class Out>
-  __device__ static void obs_out(const double* s, Out out) {
-    double o[OBS];
-    reacher_obs(s, o);
-#pragma unroll
-    for (int k = 0; k < OBS; ++k) out(k, o[k]);
-  }
-};
-template <>
-struct EnvC<MRL_ENV_SWIMMER> {
-  static constexpr int NS = SW_NS, OBS = SW_OBS, ACT = SW_ACT, DISCRETE = 0, MAX_STEPS = SW_MAX_STEPS, NU = SW_NU,
-                       OBS_SLOTS = 0;
-  __device__ static void reset(const double* u, double* s) { swimmer_reset(u, s); }
-  __device__ static void obs(const double* s, double* o) { swimmer_obs(s, o); }
-  __device__ static void step_disc(double*, int, double&, bool&) {}
-  __device__ static void step_cont(double* s, const float* a, double& rew, bool& done) { swimmer_step(s, a, rew, done); }
-  __device__ static void step_cont_quad(double* s, const float* a, double& rew, bool& done, int, const double*) {
-    swimmer_step(s, a, rew, done);
-  }
-  template <class Out>
-  __device__ static void obs_out(const double* s, Out out) {
-    double o[OBS];
-    swimmer_obs(s, o);
-#pragma unroll
-    for (int k = 0; k < OBS; ++k) out(k, o[k]);
-  }
-};
-
-// the planar tree with ground contact (envs_tree.h): a thread steps an env whole, so the four
-// rows of the fused step all step it identically, as Reacher's do
-template <>
-struct EnvC<MRL_ENV_HALFCHEETAH> {
-  static constexpr int NS = HC_NS, OBS = HC_OBS, ACT = HC_ACT, DISCRETE = 0, MAX_STEPS = HC_MAX_STEPS, NU = HC_NU,
-                       OBS_SLOTS = 0;
-  __device__ static void reset(const double* u, double* s) { halfcheetah_reset(u, s); }
-  __device__ static void obs(const double* s, double* o) { halfcheetah_obs(s, o); }
-  __device__ static void step_disc(double*, int, double&, bool&) {}
-  __device__ static void step_cont(double* s, const float* a, double& rew, bool& done) {
-    halfcheetah_step(s, a, rew, done);
-  }
-  __device__ static void step_cont_quad(double* s, const float* a, double& rew, bool& done, int, const double*) {
-    halfcheetah_step(s, a, rew, done);
-  }
-  template <class Out>
-  __device__ static void obs_out(const double* s, Out out) {
-    double o[OBS];
-    halfcheetah_obs(s, o);
-#pragma unroll
-    for (int k = 0; k < OBS; ++k) out(k, o[k]);
-  }
-};
+// keyed on the id, so that the kernel templates <int ENV> keep their names
+template <int ENV>
+struct EnvC;
+#define MRL_ENV_BIND(ID, E) \
+  template <>               \
+  struct EnvC<ID> : EnvAdaptor<E> {};
+MRL_ENV_LIST(MRL_ENV_BIND, MRL_ENV_BIND)
+#undef MRL_ENV_BIND
 
 struct EnvInfo {
   int ns, obs, act, discrete, max_steps;
 };
+template <class E>
+__host__ __device__ constexpr EnvInfo env_info_of() {
+  return EnvInfo{E::NS, E::OBS, E::ACT, E::DISCRETE, E::MAX_STEPS};
+}
+// an id that is not in the list has Hopper's row
 __host__ __device__ inline EnvInfo env_info(int id) {
-  if (id == MRL_ENV_CARTPOLE) return EnvInfo{CP_NS, CP_OBS, 2, 1, 200};
-  if (id == MRL_ENV_HUMANOID) return EnvInfo{HM_NS, HM_OBS, HM_ACT, 0, 1000};
-  if (id == MRL_ENV_PENDULUM) return EnvInfo{PD_NS, PD_OBS, PD_ACT, 0, 200};
-  if (id == MRL_ENV_MOUNTAINCAR) return EnvInfo{MC_NS, MC_OBS, 3, 1, 200};
-  if (id == MRL_ENV_ACROBOT) return EnvInfo{AC_NS, AC_OBS, 3, 1, 500};
-  if (id == MRL_ENV_INVPENDULUM) return EnvInfo{IP_NS, IP_OBS, IP_ACT, 0, 1000};
-  if (id == MRL_ENV_INVDOUBLEPENDULUM) return EnvInfo{DP_NS, DP_OBS, DP_ACT, 0, 1000};
-  if (id == MRL_ENV_REACHER) return EnvInfo{RC_NS, RC_OBS, RC_ACT, 0, RC_MAX_STEPS};
-  if (id == MRL_ENV_SWIMMER) return EnvInfo{SW_NS, SW_OBS, SW_ACT, 0, SW_MAX_STEPS};
-  if (id == MRL_ENV_HALFCHEETAH) return EnvInfo{HC_NS, HC_OBS, HC_ACT, 0, HC_MAX_STEPS};
-  return EnvInfo{HP_NS, HP_OBS, HP_ACT, 0, 1000};
+#define MRL_ENV_ROW(ID, E) \
+  if (id == ID) return env_info_of<E>();
+  MRL_ENV_LIST(MRL_ENV_ROW, MRL_ENV_ROW)
+#undef MRL_ENV_ROW
+  return env_info_of<HopperEnv>();
 }
 // the ids the entry points take (MRL_ENV_*; 3, 7, 10 and 13 are not)
 __host__ __device__ inline bool env_known(int id) {
-  return id == MRL_ENV_CARTPOLE || id == MRL_ENV_HOPPER || id == MRL_ENV_HUMANOID || id == MRL_ENV_PENDULUM ||
-         id == MRL_ENV_MOUNTAINCAR || id == MRL_ENV_ACROBOT || id == MRL_ENV_INVPENDULUM ||
-         id == MRL_ENV_INVDOUBLEPENDULUM || id == MRL_ENV_REACHER || id == MRL_ENV_SWIMMER ||
-         id == MRL_ENV_HALFCHEETAH;
+#define MRL_ENV_ROW(ID, E) \
+  if (id == ID) return true;
+  MRL_ENV_LIST(MRL_ENV_ROW, MRL_ENV_ROW)
+#undef MRL_ENV_ROW
+  return false;
 }
 __host__ __device__ inline int filt_doubles(int obs) { return 2 + 2 * (obs + 1); }
 
@@ -415,7 +256,7 @@ __device__ inline void sample_and_step(const RollArgs& a, int64_t row, const flo
 #pragma unroll
       for (int q = 0; q < A; ++q) a.b.prob[row * A + q] = p[q];
     }
-    EC::step_disc(s, act, rew, done);
+    EC::step(s, act, rew, done);
   } else {
     float av[A];
 #pragma unroll
@@ -429,7 +270,7 @@ __device__ inline void sample_and_step(const RollArgs& a, int64_t row, const flo
       }
     }
     if constexpr (QUAD) EC::step_cont_quad(s, av, rew, done, h, capc);
-    else EC::step_cont(s, av, rew, done);
+    else EC::step(s, av, rew, done);
   }
 }
 

@@ -1,7 +1,8 @@
 // Host-side glue shared by the rollout units -- rollout.hip, rollout_layered.hip, env_api.hip
-// and the population rollout in cem.hip: the descriptor checks, the launch arguments, the
-// dispatch of an env id or a flag onto a kernel template, and the launch of the Humanoid
-// wave-per-env kernels.  The error state (fail / hip_check, mrl_common.h) is mlp_kernels.hip's.
+// and the population rollouts pop_rollout*.hip: the descriptor checks, the launch arguments,
+// the dispatch of an env id (over rollout_device.h's MRL_ENV_LIST) or a flag onto a kernel
+// template, and the launch of the Humanoid wave-per-env kernels.  The error state (fail /
+// hip_check, mrl_common.h) is mlp_kernels.hip's.
 #pragma once
 #include <stdlib.h>
 
@@ -55,40 +56,28 @@ inline int check_fused_run(const mrl_rollout_desc* d, const mrl_mlp_desc* pol, c
 }
 
 // ------------------------------------------------------------------ dispatch
-// A kernel template <int ENV> launched for a run-time env id: every env ...
-#define MRL_DISPATCH_ENV(id, KERNEL, ...)                                                          \
-  do {                                                                                            \
-    if ((id) == MRL_ENV_CARTPOLE) hipLaunchKernelGGL(KERNEL<MRL_ENV_CARTPOLE>, __VA_ARGS__);       \
-    else if ((id) == MRL_ENV_HOPPER) hipLaunchKernelGGL(KERNEL<MRL_ENV_HOPPER>, __VA_ARGS__);      \
-    else if ((id) == MRL_ENV_PENDULUM) hipLaunchKernelGGL(KERNEL<MRL_ENV_PENDULUM>, __VA_ARGS__);  \
-    else if ((id) == MRL_ENV_MOUNTAINCAR)                                                         \
-      hipLaunchKernelGGL(KERNEL<MRL_ENV_MOUNTAINCAR>, __VA_ARGS__);                               \
-    else if ((id) == MRL_ENV_ACROBOT) hipLaunchKernelGGL(KERNEL<MRL_ENV_ACROBOT>, __VA_ARGS__);    \
-    else if ((id) == MRL_ENV_INVPENDULUM)                                                         \
-      hipLaunchKernelGGL(KERNEL<MRL_ENV_INVPENDULUM>, __VA_ARGS__);                               \
-    else if ((id) == MRL_ENV_INVDOUBLEPENDULUM)                                                   \
-      hipLaunchKernelGGL(KERNEL<MRL_ENV_INVDOUBLEPENDULUM>, __VA_ARGS__);                         \
-    else if ((id) == MRL_ENV_REACHER) hipLaunchKernelGGL(KERNEL<MRL_ENV_REACHER>, __VA_ARGS__);    \
-    else if ((id) == MRL_ENV_SWIMMER) hipLaunchKernelGGL(KERNEL<MRL_ENV_SWIMMER>, __VA_ARGS__);    \
-    else if ((id) == MRL_ENV_HALFCHEETAH)                                                         \
-      hipLaunchKernelGGL(KERNEL<MRL_ENV_HALFCHEETAH>, __VA_ARGS__);                               \
-    else hipLaunchKernelGGL(KERNEL<MRL_ENV_HUMANOID>, __VA_ARGS__);                               \
-  } while (0)
+// A kernel template <int ENV> launched for a run-time env id, f(integral_constant<int, ENV>)
+// over MRL_ENV_LIST: every env (an id that is not in the list goes to Humanoid) ...
+template <class F>
+inline void dispatch_env(int id, F&& f) {
+#define MRL_ENV_CASE(ID, E) \
+  if (id == ID) return f(std::integral_constant<int, ID>{});
+  MRL_ENV_LIST(MRL_ENV_CASE, MRL_ENV_CASE)
+#undef MRL_ENV_CASE
+  f(std::integral_constant<int, MRL_ENV_HUMANOID>{});
+}
+#define MRL_DISPATCH_ENV(id, KERNEL, ...) \
+  dispatch_env((id), [&](auto env) { hipLaunchKernelGGL(KERNEL<env()>, __VA_ARGS__); })
 
 // ... or those that are stepped by a thread per env (all but Humanoid: the callers have
-// turned it away or launch its wave-per-env kernel): f(integral_constant<int, ENV>)
+// turned it away or launch its wave-per-env kernel; any other id goes to Hopper)
 template <class F>
 inline void dispatch_thread_env(int id, F&& f) {
-  if (id == MRL_ENV_CARTPOLE) f(std::integral_constant<int, MRL_ENV_CARTPOLE>{});
-  else if (id == MRL_ENV_PENDULUM) f(std::integral_constant<int, MRL_ENV_PENDULUM>{});
-  else if (id == MRL_ENV_MOUNTAINCAR) f(std::integral_constant<int, MRL_ENV_MOUNTAINCAR>{});
-  else if (id == MRL_ENV_ACROBOT) f(std::integral_constant<int, MRL_ENV_ACROBOT>{});
-  else if (id == MRL_ENV_INVPENDULUM) f(std::integral_constant<int, MRL_ENV_INVPENDULUM>{});
-  else if (id == MRL_ENV_INVDOUBLEPENDULUM) f(std::integral_constant<int, MRL_ENV_INVDOUBLEPENDULUM>{});
-  else if (id == MRL_ENV_REACHER) f(std::integral_constant<int, MRL_ENV_REACHER>{});
-  else if (id == MRL_ENV_SWIMMER) f(std::integral_constant<int, MRL_ENV_SWIMMER>{});
-  else if (id == MRL_ENV_HALFCHEETAH) f(std::integral_constant<int, MRL_ENV_HALFCHEETAH>{});
-  else f(std::integral_constant<int, MRL_ENV_HOPPER>{});
+#define MRL_ENV_CASE(ID, E) \
+  if (id == ID) return f(std::integral_constant<int, ID>{});
+  MRL_ENV_LIST(MRL_ENV_CASE, MRL_ENV_NONE)
+#undef MRL_ENV_CASE
+  f(std::integral_constant<int, MRL_ENV_HOPPER>{});
 }
 #define MRL_DISPATCH_THREAD_ENV(id, KERNEL, ...) \
   dispatch_thread_env((id), [&](auto env) { hipLaunchKernelGGL(KERNEL<env()>, __VA_ARGS__); })

@@ -103,6 +103,34 @@ def test_host_queries_match_the_reference_parameter_layout():
     assert lib.mrl_filter_doubles(_lib.ENV_CARTPOLE) == 2 + 2 * 5
 
 
+# doubles of env state per env (Humanoid: 64 of state + 565 of kinematics cache)
+ENV_STATE_DOUBLES = {"CartPole-v0": 4, "Hopper-v2": 12, "Humanoid-v2": 64 + 565, "Pendulum-v0": 2, "MountainCar-v0": 2,
+                     "Acrobot-v1": 4, "InvertedPendulum-v2": 4, "InvertedDoublePendulum-v2": 6, "Reacher-v2": 6,
+                     "Swimmer-v2": 10, "HalfCheetah-v2": 18}
+
+
+def test_python_env_table_matches_the_c_table():
+    """Every REGISTRY row (obs / act / discrete, restated for Python so that DeviceEnv works
+    without the library) against what the library's own env list answers for its id."""
+    from modular_rl_amd import _lib
+    from modular_rl_amd.envs import REGISTRY
+    from tests import cem_small_np
+    lib = _lib.load()
+    assert set(REGISTRY) == set(ENV_STATE_DOUBLES) and len(REGISTRY) == 11
+    assert len({r["kind"] for r in REGISTRY.values()}) == len(REGISTRY)
+    hid = (ctypes.c_int32 * 2)(10, 5)
+    for env_id, r in REGISTRY.items():
+        kind, O, A = r["kind"], r["obs"], r["act"]
+        assert lib.mrl_filter_doubles(kind) == 2 + 2 * (O + 1), env_id
+        assert lib.mrl_record_doubles(kind) == 2 + 2 * (O + 1), env_id
+        assert lib.mrl_env_state_doubles(kind) == ENV_STATE_DOUBLES[env_id], env_id
+        if kind == _lib.ENV_HUMANOID:
+            continue  # not a thread-per-env env: the small population rollout turns it away
+        # kernels and biases, plus logstd for a Gauss head: pins act and discrete
+        want = cem_small_np.num_params([O, 10, 5, A], not r["discrete"])
+        assert lib.mrl_pop_mlp_num_params(kind, hid, 2) == want, env_id
+
+
 def test_grids_sized_for_a_cu_subset():
     """desc.cus scales the grid caps (VF passes beside the rollout on 192 CUs): the VJP
     one block per CU, the row passes six; cus = 0 is the whole device (256)."""
