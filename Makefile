@@ -5,6 +5,7 @@ CSRC := modular_rl_amd/csrc
 SRCS := $(CSRC)/mlp_kernels.hip $(CSRC)/mlp_rows_vjp.hip $(CSRC)/mlp_vjp16.hip $(CSRC)/mlp_fisher.hip \
   $(CSRC)/mlp_bf16.hip $(CSRC)/mlp_split.hip $(CSRC)/gae.hip $(CSRC)/cg.hip $(CSRC)/episode_stats.hip \
   $(CSRC)/vector_ops.hip $(CSRC)/rollout.hip $(CSRC)/rollout_layered.hip \
+  $(CSRC)/rollout_eval.hip $(CSRC)/rollout_layered_eval.hip \
   $(CSRC)/env_api.hip $(CSRC)/gemm.hip $(CSRC)/gemm_bf16.hip $(CSRC)/gemm_bf16_big.hip \
   $(CSRC)/gemm_bf16_stream.hip $(CSRC)/gemm_bf16_tn.hip $(CSRC)/cem.hip \
   $(CSRC)/pop_rollout.hip $(CSRC)/pop_rollout_small.hip $(CSRC)/runtime.hip
@@ -24,6 +25,10 @@ all: $(LIB)
 build/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# the evaluation units compile their training unit's text (its EV kernel instantiations)
+build/rollout_eval.o build/ubsan/rollout_eval.o: $(CSRC)/rollout.hip
+build/rollout_layered_eval.o build/ubsan/rollout_layered_eval.o: $(CSRC)/rollout_layered.hip
 
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS)

@@ -452,7 +452,8 @@ typedef struct {
   uint64_t seed;           /* Philox key                                         */
   int32_t compute;         /* MRL_COMPUTE_*: the policy net's dtype; BF16 rounds the
                               fused forward's W0, W1, x, h1, h2 to bf16 like
-                              mrl_mlp_rows_bf16, so rollout prob rows = update's    */
+                              mrl_mlp_rows_bf16, so rollout prob rows = update's;
+                              optionally | MRL_ROLLOUT_EVAL (below)                */
   int32_t launch_cus;      /* mrl_rollout_run's residency check: 0 = the CUs of the
                               stream it is called on; > 0 = the CUs of the stream a
                               captured graph will be replayed on (capture streams
@@ -481,6 +482,32 @@ typedef struct {
                               rows also as bf16 (RNE; the first hidden GEMM's operand), columns
                               obs_dim.. left as they are (caller zeroes them once); NULL: none */
 } mrl_rollout_bufs;
+
+/* Evaluation mode of the rollout (the reference's `agent.stochastic = False`, sim_agent.py):
+ * desc.compute = MRL_COMPUTE_F32 | MRL_ROLLOUT_EVAL or MRL_COMPUTE_BF16 | MRL_ROLLOUT_EVAL.
+ * The desc has no spare field, and the kernels take it by value inside their launch
+ * arguments, so a new field would move every kernel's arguments; the flag is therefore a bit
+ * of `compute`, where every value but 0 and 1 was refused (MRL_E_ARG) until now -- no call
+ * that was accepted changes its meaning.  With the flag, mrl_rollout_reset / _step / _run and
+ * mrl_rollout_reset_rows / _obs / _act / _act_head / _act_head_bf16 launch the evaluation
+ * instantiations of their kernels:
+ *   action   the mode of the head (ProbType.maxprob): the Gauss mean | the arg-max logit, the
+ *            lowest index on a tie; no noise is read (bufs.noise must be NULL: a desc with the
+ *            flag and noise rows is MRL_E_ARG before any launch; mrl_rollout_noise_doubles is
+ *            0 and mrl_rollout_noise MRL_E_ARG); prob rows are written as in training
+ *   filter   desc.filter != 0: bufs.filter_state[0 .. filter_doubles) is applied frozen, as
+ *            mrl_pop_rollout applies it -- (x - M) / (sqrt(S / (n - 1)) + 1e-8) clipped at +-5,
+ *            with n_obs < 2 the raw observation clipped only -- and never written: no partial
+ *            is published, nothing is merged, bufs.records is not touched.  desc.filter == 0:
+ *            the raw observation, as in training
+ *   rewards  raw, as in training; the reward stat is not updated
+ *   envs     stepping, ep_t, flags, auto-reset and the reset stream are the training kernels'
+ * mrl_rollout_run(persistent != 0) is one launch whose blocks share nothing: it needs no
+ * workspace (sync may be NULL and is not written) and no resident grid, so it never falls
+ * back.  mrl_rollout_finish has nothing to fold and launches nothing (the iteration counter,
+ * the sampling noise's step base, stays).  The stand-alone env stepper and the population
+ * rollouts ignore the flag. */
+#define MRL_ROLLOUT_EVAL 0x100
 
 /* env_state doubles per env (Humanoid: qpos ++ qvel ++ ctrl, 64, plus the 565-double
    kinematics cache the step kernels keep of the stored state) */

@@ -26,6 +26,7 @@ ENV_HALFCHEETAH = 14  # 13 is not an env
 GEMM_STORE, GEMM_TANH, GEMM_DTANH, GEMM_SLAB = 0, 1, 2, 3
 COMPUTE_F32, COMPUTE_BF16, COMPUTE_SPLIT = 0, 1, 2
 COMPUTE = {"fp32": COMPUTE_F32, "bf16": COMPUTE_BF16}
+ROLLOUT_EVAL = 0x100  # MRL_ROLLOUT_EVAL: or-ed into RolloutDesc.compute, the rollout's evaluation mode
 
 vp = ctypes.c_void_p
 i32 = ctypes.c_int32

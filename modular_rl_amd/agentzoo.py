@@ -111,31 +111,51 @@ class TrpoAgent(AgentWithPolicy):
         AgentWithPolicy.__init__(self, policy, obfilter, rewfilter)
 
     # ---- device collection
-    def make_collector(self, env, cfg=None, n_envs=None, horizon=None, timestep_limit=None):
+    def make_collector(self, env, cfg=None, n_envs=None, horizon=None, timestep_limit=None, evaluate=None):
+        """``evaluate``: an evaluation collector (``Collector(evaluate=True)``: the head's mode,
+        the filter frozen); ``None`` follows ``self.stochastic``, so ``set_stochastic(False)``
+        and then ``make_collector`` evaluates.  The mode is part of the cache key.  An
+        evaluation collector reads the agent's one ``filter_state`` tensor and the policy's
+        theta and writes neither; its env state, episode counters and reset stream are its own
+        (seed ``self.seed + 1``), so evaluating between training iterations leaves training
+        bit for bit as it was."""
         cfg = self.cfg if cfg is None else cfg
+        evaluate = (not self.stochastic) if evaluate is None else bool(evaluate)
         E = int(n_envs or cfg.get("n_envs", 1) or 1)
         T = int(horizon or horizon_of(cfg))
         limit = int(timestep_limit or cfg["timestep_limit"] or env.spec.max_episode_steps)
-        key = (env.spec.id, E, T, limit)
+        key = self.collector_key(env.spec.id, E, T, limit, evaluate)
         if key not in self._collectors:
-            col = Collector(env, self.policy, E, T, limit, filter=self.cfg["filter"], seed=self.seed, comm=self.comm,
-                            use_graph=bool(cfg.get("use_graph", self.cfg.get("use_graph", 1))))
-            shared = self._filter_owner()
+            col = Collector(env, self.policy, E, T, limit, filter=self.cfg["filter"],
+                            seed=self.seed + (1 if evaluate else 0), comm=self.comm,
+                            use_graph=bool(cfg.get("use_graph", self.cfg.get("use_graph", 1))), evaluate=evaluate)
+            shared = self._filter_owner(any_mode=True)
             if shared is not None:  # one running stat per agent
                 col.filter_state = shared.filter_state
-            elif self._pending_state:
+            if self._pending_state:
+                # a loaded snapshot: the filter state for the first collector of the agent, the
+                # RNG counters for its first training collector (apply_collector_state)
                 from .checkpoint import apply_collector_state
-                apply_collector_state(col, self._pending_state)
-                self._pending_state = None
+                self._pending_state = apply_collector_state(col, self._pending_state)
             self._collectors[key] = col
         return self._collectors[key]
+
+    @staticmethod
+    def collector_key(env_id, n_envs, horizon, timestep_limit, evaluate):
+        return (env_id, int(n_envs), int(horizon), int(timestep_limit)) + (("evaluate",) if evaluate else ())
 
     def path_collector(self, env, timestep_limit):
         return self.make_collector(env, n_envs=1, horizon=int(timestep_limit), timestep_limit=timestep_limit)
 
-    def _filter_owner(self):
+    def _filter_owner(self, any_mode=False):
+        """The collector whose filter state and RNG counters are the agent's: its first training
+        collector (``any_mode``: else its first evaluation one, which shares the filter state)."""
         for c in self._collectors.values():
-            return c
+            if not c.evaluate:
+                return c
+        for c in self._collectors.values():
+            if any_mode:
+                return c
         return None
 
 

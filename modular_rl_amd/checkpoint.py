@@ -172,8 +172,17 @@ def load_snapshot(path, agent):
 
 
 def apply_collector_state(col, st):
+    """Restore a snapshot's filter state and RNG counters into ``col``; returns what is left
+    for a later collector, or None.  An evaluation collector (``col.evaluate``) takes the filter
+    state only -- into the one tensor the agent's collectors share; its envs and reset stream
+    are its own -- and leaves the RNG counters for the agent's first training collector."""
     if not st:
-        return
+        return None
+    if getattr(col, "evaluate", False):
+        rest = {k: v for k, v in st.items() if k != "filter/state"}
+        st = {k: v for k, v in st.items() if k == "filter/state"}
+    else:
+        rest = None
     if "filter/state" in st:
         fs = torch.as_tensor(st["filter/state"], dtype=torch.float64)
         if fs.numel() != col.FS:
@@ -186,6 +195,7 @@ def apply_collector_state(col, st):
         if ep.numel() != col.E:
             raise ValueError(f"snapshot has episode counters for {ep.numel()} envs, this collector steps {col.E}")
         col.env_int[col.E:].copy_(ep.to(col.env_int.device))
+    return rest or None
 
 
 class RunLog:

@@ -159,10 +159,18 @@ class Batch:
 
 
 class Collector:
+    """``evaluate=True``: the rollout's evaluation mode (MRL_ROLLOUT_EVAL, include/mrl_hip.h; the
+    reference's ``agent.stochastic = False``) on every launch -- step launches, graph replay,
+    the persistent launch, the layered and the Humanoid path.  The action is the head's mode
+    and no noise is drawn (``set_noise`` raises); ``filter_state`` is applied frozen and never
+    written (``filter_stats()`` answers from the unchanged state, nothing is merged across
+    ranks); rewards are raw; envs, counters and the reset stream advance as in training."""
+
     def __init__(self, env, policy, n_envs, horizon, timestep_limit, filter=1, seed=0, comm=None, device="cuda",
-                 use_graph=False):
+                 use_graph=False, evaluate=False):
         lib = _lib.load(require_gpu=True)
         self.env, self.policy = env, policy
+        self.evaluate = bool(evaluate)
         self.comm = comm if comm is not None else Comm()
         self.E, self.T = int(n_envs), int(horizon)
         self.N = self.E * self.T
@@ -173,7 +181,8 @@ class Collector:
         self.dev = torch.device(device)
         self.desc = _lib.RolloutDesc(env.kind, self.E, self.T, int(timestep_limit), int(filter),
                                      self.comm.rank * self.E, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                     _lib.COMPUTE[getattr(policy.net, "dtype", "fp32")], 0)
+                                     _lib.COMPUTE[getattr(policy.net, "dtype", "fp32")]
+                                     | (_lib.ROLLOUT_EVAL if self.evaluate else 0), 0)
         ns = lib.mrl_env_state_doubles(env.kind)
         self.FS = int(lib.mrl_filter_doubles(env.kind))
         self.RS = int(lib.mrl_record_doubles(env.kind))
@@ -238,17 +247,17 @@ class Collector:
         self._graph_cus = None
 
     def _bufs(self):
+        noise = None if self.evaluate else (self.noise if self.noise is not None else self._noise_rows)
         return _lib.RolloutBufs(ptr(self.env_state), ptr(self.env_int), ptr(self.filter_state), ptr(self.records),
                                 ptr(self.iteration), ptr(self.obs), ptr(self.act), ptr(self.prob), ptr(self.rew),
-                                ptr(self.flags), ptr(self.ep_t),
-                                ptr(self.noise if self.noise is not None else self._noise_rows), ptr(self.stamps),
+                                ptr(self.flags), ptr(self.ep_t), ptr(noise), ptr(self.stamps),
                                 ptr(self.raw_obs), ptr(self._xb16 if self.hidden_b16 else None))
 
     def fill_noise(self):
         """This iteration's sampling noise, one parallel draw over every row (no-op when
         noise is injected).  Issued outside the captured step graph so the pipelined
         loop can run it on all CUs while the step chain runs on the rollout's CU set."""
-        if self.noise is None:
+        if self.noise is None and not self.evaluate:
             call("mrl_rollout_noise", ctypes.byref(self.desc), ctypes.byref(self._bufs()), ptr(self._noise_rows),
                  stream())
 
@@ -263,6 +272,8 @@ class Collector:
         # persistent is off / the stream has too few CUs; identical results)
         call("mrl_rollout_run", ctypes.byref(self.desc), ctypes.byref(net.desc), ptr(net.theta), ptr(self._rimage),
              ctypes.byref(bufs), ptr(self._sync), int(self.persistent), stream())
+        if self.evaluate:
+            return  # its persistent launch hands nothing over (nothing to abort), and nothing is left to fold
         if self.persistent:
             torch.maximum(self.status, self._sync[32:33], out=self.status)
         call("mrl_rollout_finish", ctypes.byref(self.desc), ctypes.byref(bufs), stream())
@@ -293,10 +304,13 @@ class Collector:
                 net.forward_rows(x, E, self._zrows, self._fwd_bufs)
                 call("mrl_rollout_act", d, int(net.head), int(net.n_out), ptr(self._zrows), logstd,
                      ctypes.byref(bufs), int(t), stream())
-        call("mrl_rollout_finish", d, ctypes.byref(bufs), stream())
+        if not self.evaluate:
+            call("mrl_rollout_finish", d, ctypes.byref(bufs), stream())
 
     def set_noise(self, noise):
         """Inject sampling noise (float64 u[N] or z[N, d]) instead of Philox (parity mode)."""
+        if self.evaluate:
+            raise _lib.MrlError("set_noise: an evaluation collector takes the head's mode and reads no noise")
         self.noise = None if noise is None else torch.as_tensor(noise, dtype=torch.float64).to(self.dev).contiguous()
         self.graph = None
 
@@ -310,7 +324,7 @@ class Collector:
         if fill_noise:
             self.fill_noise()
         self.rows_gen += 1
-        self._fs_start = self.filter_state[:self.FS].clone() if self.comm.enabled else None
+        self._fs_start = self.filter_state[:self.FS].clone() if self.comm.enabled and not self.evaluate else None
         # the persistent launch's residency check counts the CUs of the stream it runs on:
         # the stream of this call (a captured graph replays here, not on its capture stream)
         from . import streams
@@ -360,7 +374,7 @@ class Collector:
         """Cross-rank filter merge (waits for the rollout) and the iteration's Batch.  The
         batch carries the device abort status, which the policy update reads back with its
         step scalars before it touches theta."""
-        if self.comm.enabled:
+        if self.comm.enabled and not self.evaluate:
             # the merge synchronises on the rollout anyway: an aborted rollout must not
             # merge its partial filter deltas into every rank's filter
             self.check()
@@ -368,7 +382,7 @@ class Collector:
         b = Batch(self.N, self.obs, self.act, self.prob, self.rew, self.flags, self.ep_t, T=self.T, E=self.E)
         b.n_global = self.N_global
         b.rows_owner, b.rows_gen = self, self.rows_gen
-        if not self.layered and self.persistent:
+        if not self.layered and self.persistent and not self.evaluate:
             b.abort, b.abort_msg = self.status, self.ABORT_MSG
         return b
 

@@ -147,6 +147,9 @@ PG_OPTIONS = [
     ("horizon", int, 0, "steps per env per iteration (0: ceil(timesteps_per_batch / n_envs))"),
     ("use_graph", int, 1, "replay the rollout's per-step launches from one captured hipGraph"),
     ("pipeline", int, 1, "run the VF fit of iteration k beside the rollout of iteration k+1 on disjoint CUs"),
+    ("eval_every", int, 0, "every K iterations, score the policy deterministically (evaluate_agent): "
+                           "eval_EpRewMean / eval_EpLenMean / eval_NumEp in the stats; 0: off"),
+    ("eval_envs", int, 0, "envs of that evaluation, one whole episode each (0: min(n_envs, 256))"),
 ]
 
 
@@ -157,18 +160,75 @@ def horizon_of(cfg):
     return max(h, 1)
 
 
+def evaluate_agent(env, agent, n_envs, n_episodes_per_env=1, timestep_limit=None):
+    """Deterministic score of ``agent``'s policy (the reference's sim_agent.py loop,
+    ``agent.stochastic = False``, without the rendering): whole episodes of ``n_envs`` envs in
+    lock-step on an evaluation collector (``make_collector(evaluate=True)``: the head's mode,
+    the agent's filter state applied frozen, raw rewards) until every env has finished
+    ``n_episodes_per_env`` of them.  One collect of ``timestep_limit`` steps resets every env
+    and so finishes each env's first episode (an episode is at most ``timestep_limit`` long);
+    that episode is the one taken, ``n_episodes_per_env`` collects give as many per env, each
+    from the env's next reset draw.  What a collect steps after an env's first episode end is
+    dropped: zeroing those rows' flags leaves the run open, which the episode-stats scan
+    (mrl_episode_stats) does not count.
+
+    Returns a dict: ``EpisodeRewards`` / ``EpisodeLengths`` (numpy, [n_episodes_per_env * n_envs],
+    collect-major), ``NumEp``, ``EpRewMean``, ``EpRewSEM``, ``EpRewMax``, ``EpLenMean`` -- the
+    scalars from the scan's sums over all collects, the per-episode arrays from the same masked
+    rows.  Nothing of the agent changes: not theta, not the filter state, not a training
+    collector's envs or counters.  This rank's episodes only."""
+    limit = int(timestep_limit or agent.cfg["timestep_limit"] or env.spec.max_episode_steps)
+    E, K = int(n_envs), int(n_episodes_per_env)
+    if E <= 0 or K <= 0:
+        raise ValueError("evaluate_agent: n_envs and n_episodes_per_env must be positive")
+    col = agent.make_collector(env, n_envs=E, horizon=limit, timestep_limit=limit, evaluate=True)
+    T = col.T
+    t_idx = torch.arange(T, device=col.dev).view(T, 1)
+    sums = torch.zeros(6, dtype=torch.float64, device=col.dev)
+    rets, lens = [], []
+    for _ in range(K):
+        b = col.collect()
+        ends = (b.flags.view(T, E) & 1) != 0
+        first = torch.argmax(ends.to(torch.uint8), dim=0)  # the horizon cut ends every column
+        keep = t_idx <= first.view(1, E)
+        flags = torch.where(keep, b.flags.view(T, E), torch.zeros_like(b.flags.view(T, E))).contiguous()
+        call("mrl_episode_stats", ptr(b.rew), ptr(flags), T, E, ptr(col._ep_out), ptr(col._ep_ws), stream())
+        s = col._ep_out[:6]
+        sums[[0, 1, 2, 4]] += s[[0, 1, 2, 4]]
+        sums[[3, 5]] = torch.maximum(sums[[3, 5]], s[[3, 5]]) if rets else s[[3, 5]]
+        rets.append((b.rew.view(T, E).double() * keep).sum(0))
+        lens.append(first + 1)
+    cnt, sr, sr2, mr, sl, _ = (float(x) for x in sums.cpu().numpy())
+    assert int(cnt) == K * E, (cnt, K, E)
+    mean = sr / cnt
+    return dict(EpisodeRewards=torch.cat(rets).cpu().numpy(), EpisodeLengths=torch.cat(lens).cpu().numpy(),
+                NumEp=int(cnt), EpRewMean=mean,
+                EpRewSEM=float(np.sqrt(max(sr2 / cnt - mean * mean, 0.0)) / np.sqrt(cnt)), EpRewMax=mr,
+                EpLenMean=sl / cnt)
+
+
 def run_policy_gradient_algorithm(env, agent, usercfg=None, callback=None):
-    """`core.py:118-171`: rollouts -> advantage -> VF fit -> TRPO update -> callback(stats)."""
+    """`core.py:118-171`: rollouts -> advantage -> VF fit -> TRPO update -> callback(stats).
+    ``eval_every`` = K > 0: after every K-th update the policy it left is scored by
+    evaluate_agent on ``eval_envs`` envs, and the iteration's stats gain eval_EpRewMean,
+    eval_EpLenMean and eval_NumEp.  The evaluation is issued once the rollout already in flight
+    (the pipelined loop's next one) has finished, so it reads the filter state at an iteration
+    boundary; it changes nothing the training reads."""
     cfg = update_default_config(PG_OPTIONS, usercfg)
     cfg.update(usercfg or {})
     if cfg["parallel"]:
         raise NotImplementedError("parallel rollouts: launch one process per GPU with torchrun instead")
     comm = agent.comm
-    collector = agent.make_collector(env, cfg)
+    collector = agent.make_collector(env, cfg, evaluate=False)
     runner = IterationRunner(agent, collector, cfg, comm, pipeline=bool(cfg["pipeline"]))
     tstart = time.time()
+    eval_every = int(cfg.get("eval_every", 0) or 0)
+    eval_envs = int(cfg.get("eval_envs", 0) or 0) or min(collector.E, 256)
+    evals, emitted = {}, [0]
 
     def emit(stats):
+        add_prefixed_stats(stats, "eval", evals.pop(emitted[0], {}))
+        emitted[0] += 1
         stats["TimeElapsed"] = time.time() - tstart
         if callback:
             callback(stats)
@@ -176,9 +236,17 @@ def run_policy_gradient_algorithm(env, agent, usercfg=None, callback=None):
         # after this callback must read the live state
         agent._snapshot_capture = None
 
+    def evaluate(i):
+        if runner.pipeline:
+            torch.cuda.current_stream().wait_stream(runner.rollout_stream)
+        ev = evaluate_agent(env, agent, eval_envs, timestep_limit=collector.desc.timestep_limit)
+        evals[i] = {k: ev[k] for k in ("EpRewMean", "EpLenMean", "NumEp")}
+
     with runner.loop_stream():
         for i in range(cfg["n_iter"]):
             done = runner.step(prelaunch_next=i + 1 < cfg["n_iter"])
+            if eval_every > 0 and (i + 1) % eval_every == 0:
+                evaluate(i)
             if done is not None:
                 emit(done)
         done = runner.drain()

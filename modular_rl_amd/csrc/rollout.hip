@@ -464,15 +464,26 @@ __global__ void noise_fill_kernel(RollArgs a, double* __restrict__ out) {
   }
 }
 
-template <int ENV>
+// EV (here and in the two kernels below): the evaluation instantiation (MRL_ROLLOUT_EVAL,
+// rollout_device.h) -- the envs' reset alone, no partial of obs_0
+template <int ENV, bool EV = false>
 __global__ __launch_bounds__(RB) void rollout_reset_kernel(RollArgs a) {
   using EC = EnvC<ENV>;
   constexpr int O = EC::OBS, D = O + 1;
   static_assert(D <= 2 * COLS, "two column passes");
-  __shared__ double vals[ENVS_PER_BLOCK * col_slots(D)];
   const int E = a.d.n_envs;
   const int le = threadIdx.x;
   const int e = blockIdx.x * ENVS_PER_BLOCK + le;
+  if constexpr (EV) {
+    if (le < ENVS_PER_BLOCK && e < E) {
+      double s[EC::NS];
+      reset_env<ENV>(a, e, s);
+#pragma unroll
+      for (int i = 0; i < EC::NS; ++i) a.b.env_state[(int64_t)i * E + e] = s[i];
+    }
+    return;
+  }
+  __shared__ double vals[ENVS_PER_BLOCK * col_slots(D)];
   if (le < ENVS_PER_BLOCK && e < E) {
     double s[EC::NS], o[O];
     reset_env<ENV>(a, e, s);
@@ -489,6 +500,7 @@ __global__ __launch_bounds__(RB) void rollout_reset_kernel(RollArgs a) {
   if constexpr (D > COLS) publish_partial<COLS>(a, vals, nvalid, D, false, a.b.records);
 }
 
+#ifndef MRL_ROLLOUT_EVAL_UNIT
 // rollout image: rimage_value (mlp_layout.h) of every element
 // part p (0, 1, 2) of an f32 value's exact three-way bf16 split (mlp_split.hip)
 __device__ inline float rb_part(float v, int p) {
@@ -524,17 +536,18 @@ __global__ void rollout_pack_kernel(RDims r, MlpDims d, const float* __restrict_
                              ((uint32_t)__builtin_bit_cast(uint16_t, hi) << 16));
   }
 }
+#endif  // MRL_ROLLOUT_EVAL_UNIT
 
 // One launch = step t of E envs: 4 waves x 16 envs per block, the four 16-lane rows of
 // a wave share the wave's 16 envs (split angle functions / noise / obs columns, the
 // MFMA tiles of forward16).
-template <int ENV, bool BF>
+template <int ENV, bool BF, bool EV = false>
 __global__ __launch_bounds__(RB) void rollout_step_kernel(RollArgs a, const float* __restrict__ logstd,
                                                           const float* __restrict__ rimg, int t) {
   using EC = EnvC<ENV>;
   constexpr int O = EC::OBS, D = O + 1, NS = EC::NS, A = EC::ACT;
   static_assert(D <= 2 * COLS, "two column passes");
-  __shared__ double vals[ENVS_PER_BLOCK * col_slots(D)];
+  __shared__ double vals[EV ? 1 : ENVS_PER_BLOCK * col_slots(D)];
   __shared__ double fmean[col_slots(D)], fden[col_slots(D)];
   __shared__ float xt[4][16][MAX_IN + 1];  // +1: conflict-free column reads
   // diagnostic phase stamps (100 MHz realtime) of block 0 / thread 0 -- never set in production
@@ -564,7 +577,12 @@ __global__ __launch_bounds__(RB) void rollout_step_kernel(RollArgs a, const floa
   const bool kcol = k < D, isr = (k == O), one_round = a.nb <= 16 * RB_MAX;
   RecRound rr;
   double fn = 0.0, fM = 0.0, fS = 0.0;
-  if (kcol) {
+  if constexpr (EV) {
+    // the frozen filter: thread c < O takes column c's mean and denominator (in fM, fS) from
+    // the state, which stays as it is -- no record is read, the 16-lane column groups have
+    // nothing to do
+    if ((int)threadIdx.x < O) frozen_filter_column(a.b.filter_state, D, threadIdx.x, fM, fS);
+  } else if (kcol) {
     if (one_round) rr.load(rec_in, a.nb, a.RS, D, O, k, jj, 0);
     fn = fs_in[isr ? 1 : 0];
     fM = fs_in[2 + k];
@@ -574,7 +592,8 @@ __global__ __launch_bounds__(RB) void rollout_step_kernel(RollArgs a, const floa
 #pragma unroll
   for (int i = 0; i < NS; ++i) s[i] = valid ? a.b.env_state[(int64_t)i * E + e] : 0.0;
   double zn[A + 1] = {};
-  if (valid) load_noise<ENV>(a, row, zn);
+  if constexpr (!EV)
+    if (valid) load_noise<ENV>(a, row, zn);
   RollWeights<O, A, BF> wt;
   wt.load(rimg, lane);
   __shared__ bf16x8 w1s_l[BF ? 1 : 3 * 8 * 64];  // fp32 mode: the split W1 fragments (24 KB)
@@ -590,7 +609,12 @@ __global__ __launch_bounds__(RB) void rollout_step_kernel(RollArgs a, const floa
 
   // 2. running-stat merge (filters.py:30-31 push, per step over all envs): the block
   //    partials -> one batch -> one Chan merge; every block derives the same state
-  if (kcol) {
+  if constexpr (EV) {
+    if ((int)threadIdx.x < O) {
+      fmean[threadIdx.x] = fM;
+      fden[threadIdx.x] = fS;
+    }
+  } else if (kcol) {
     double bn, bm, bs;
     if (one_round) rr.batch(bn, bm, bs);
     else batch_of_records(rec_in, a.nb, a.RS, D, O, k, jj, bn, bm, bs);
@@ -607,7 +631,7 @@ __global__ __launch_bounds__(RB) void rollout_step_kernel(RollArgs a, const floa
       fden[k] = sqrt(var) + 1e-8;
     }
   }
-  if constexpr (D > COLS) {  // the columns past the 16 thread groups: a second pass by the first groups
+  if constexpr (D > COLS && !EV) {  // the columns past the 16 thread groups: a second pass by the first groups
     const int k2 = k + COLS;
     if (k2 < D) {
       const bool isr2 = (k2 == O);
@@ -660,6 +684,11 @@ __global__ __launch_bounds__(RB) void rollout_step_kernel(RollArgs a, const floa
   // 5. sample + env step: every row steps the env (split angle functions), row 0 stores
   double rew = 0.0;
   bool done = false;
+  if constexpr (EV) {  // the head's mode; the bookkeeping below is the training step's, no partial follows
+    mode_and_step<ENV, true>(a, row, z, lsd, s, rew, done, valid && g == 0, g);
+    if (valid && g == 0) finish_env_step<ENV>(a, e, row, t, s, rew, done);
+    return;
+  }
   sample_and_step<ENV, true>(a, row, z, lsd, zn, s, rew, done, valid && g == 0, g);
   STAMP(5);
   if (valid && g == 0) {
@@ -799,14 +828,20 @@ __device__ __attribute__((always_inline)) inline void episode_start_state(const 
 // ST: the diagnostic build with phase stamps (launched only when bufs.stamps is set);
 // production launches carry no stamp code, whose uniform pointers / offsets cost SGPRs
 // that the compiler then spilled to VGPR lanes (a v_readlane per reload, every step).
-template <int ENV, bool BF, bool ST>
+// EV: the filter is frozen, so a step has no cross-block dependency left -- the episode
+// bookkeeping is each env's own registers.  The evaluation instantiation therefore drops the
+// hand-off whole (no granule is published or polled, `sync` is not touched, no block waits
+// for another and the grid need not be resident) and with it both per-step barriers: fmean /
+// fden are written once before the loop, and a wave reads only its own rows of xt.
+template <int ENV, bool BF, bool ST, bool EV = false>
 __global__ __launch_bounds__(RB) void rollout_persistent_kernel(RollArgs a, const float* __restrict__ logstd,
                                                                 const float* __restrict__ rimg,
                                                                 uint32_t* __restrict__ sync) {
   using EC = EnvC<ENV>;
   constexpr int O = EC::OBS, D = O + 1, NS = EC::NS, A = EC::ACT;
   static_assert(D <= 2 * COLS, "two column passes");
-  __shared__ double vals[ENVS_PER_BLOCK * col_slots(D)];
+  static_assert(!(EV && ST), "the phase stamps are the training launch's");
+  __shared__ double vals[EV ? 1 : ENVS_PER_BLOCK * col_slots(D)];
   __shared__ double fmean[col_slots(D)], fden[col_slots(D)];
   __shared__ float xt[4][16][MAX_IN + 1];  // +1: conflict-free column reads
   __shared__ int s_fail;
@@ -826,7 +861,7 @@ __global__ __launch_bounds__(RB) void rollout_persistent_kernel(RollArgs a, cons
   const bool valid = e < E;
   const int ec = valid ? e : E - 1;  // invalid lanes shadow a valid env, store nothing
   const int k = threadIdx.x >> 4, jj = threadIdx.x & 15;
-  const bool kcol = k < D, isr = (k == O);
+  const bool kcol = !EV && k < D, isr = (k == O);  // EV: no column group has a column to merge
   const int nvalid = min(ENVS_PER_BLOCK, E - (int)blockIdx.x * ENVS_PER_BLOCK);
   const Granules gr(sync, nb, D);
   if (threadIdx.x == 0) s_fail = 0;
@@ -848,16 +883,24 @@ __global__ __launch_bounds__(RB) void rollout_persistent_kernel(RollArgs a, cons
   }
   // the running stat at the start of the iteration (every block keeps the same copy)
   double fn = 0.0, fM = 0.0, fS = 0.0;
-  if (kcol) {
+  if constexpr (EV) {
+    // the frozen filter, for all T steps: thread c < O writes column c's mean and denominator
+    // (the barrier after the reset below publishes them); the column groups do nothing
+    if ((int)threadIdx.x < O) {
+      frozen_filter_column(a.b.filter_state, D, threadIdx.x, fM, fS);
+      fmean[threadIdx.x] = fM;
+      fden[threadIdx.x] = fS;
+    }
+  } else if (kcol) {
     fn = a.b.filter_state[isr ? 1 : 0];
     fM = a.b.filter_state[2 + k];
     fS = a.b.filter_state[2 + D + k];
   }
   // the columns past the 16 thread groups (D > COLS): a second pass by the first groups
   const int k2 = k + COLS;
-  const bool kcol2 = D > COLS && k2 < D, isr2 = (k2 == O);
+  const bool kcol2 = !EV && D > COLS && k2 < D, isr2 = (k2 == O);
   double fn2 = 0.0, fM2 = 0.0, fS2 = 0.0;
-  if constexpr (D > COLS) {
+  if constexpr (D > COLS && !EV) {
     if (kcol2) {
       fn2 = a.b.filter_state[isr2 ? 1 : 0];
       fM2 = a.b.filter_state[2 + k2];
@@ -874,16 +917,20 @@ __global__ __launch_bounds__(RB) void rollout_persistent_kernel(RollArgs a, cons
   epc += 1u;
   episode_start_state<ENV>(a, ec, epc, sn);
   bool refill = false;
-  if (valid && g == 0) {
-    double o[O];
-    EC::obs(s, o);
+  if constexpr (!EV) {
+    if (valid && g == 0) {
+      double o[O];
+      EC::obs(s, o);
 #pragma unroll
-    for (int c = 0; c < O; ++c) vals[le * D + c] = o[c];
-    vals[le * D + O] = 0.0;
+      for (int c = 0; c < O; ++c) vals[le * D + c] = o[c];
+      vals[le * D + O] = 0.0;
+    }
   }
   __syncthreads();
-  publish_granules(gr, vals, nvalid, 0);  // gather step 0's partials
-  if constexpr (D > COLS) publish_granules<COLS>(gr, vals, nvalid, 0);
+  if constexpr (!EV) {
+    publish_granules(gr, vals, nvalid, 0);  // gather step 0's partials
+    if constexpr (D > COLS) publish_granules<COLS>(gr, vals, nvalid, 0);
+  }
   double capr[6];  // row g's capsule constants
 #pragma unroll
   for (int f = 0; f < 6; ++f) capr[f] = hp_cap[4 * f + g];
@@ -894,7 +941,7 @@ __global__ __launch_bounds__(RB) void rollout_persistent_kernel(RollArgs a, cons
     if (ST && threadIdx.x == 0 && blockIdx.x == 0)  // shader clock beside the 100 MHz one (in-kernel GHz)
       a.b.stamps[(int64_t)t * 16 + 9] = (int64_t)__builtin_amdgcn_s_memtime();
     double zn[A + 1] = {};
-    load_noise<ENV>(a, (int64_t)t * E + ec, zn);  // independent of the hand-off: issued first
+    if constexpr (!EV) load_noise<ENV>(a, (int64_t)t * E + ec, zn);  // independent of the hand-off: issued first
     // the next episode's start state of envs that auto-reset at step t-1: off the step's
     // critical path, under the first poll of the hand-off (or beside it, non-polling waves)
     auto refill_next = [&]() {
@@ -938,7 +985,7 @@ __global__ __launch_bounds__(RB) void rollout_persistent_kernel(RollArgs a, cons
         fden[k] = sqrt(var) + 1e-8;
       }
     }
-    if constexpr (D > COLS) {
+    if constexpr (D > COLS && !EV) {
       // kcol2 is uniform in a 16-lane group, not in a wave (it holds for half of wave 0), and so
       // is kcol where D is no multiple of 4: everything below works per 16-lane group
       if (kcol2) {
@@ -970,8 +1017,10 @@ __global__ __launch_bounds__(RB) void rollout_persistent_kernel(RollArgs a, cons
       }
     }
     PSTAMP(t, 8);
-    __syncthreads();
-    if (s_fail) break;  // uniform: a block that gave up leaves the loop whole
+    if constexpr (!EV) {
+      __syncthreads();
+      if (s_fail) break;  // uniform: a block that gave up leaves the loop whole
+    }
     PSTAMP(t, 1);
     // filtered observation (core.py:191-192); row g takes columns 4i + g
     {
@@ -999,7 +1048,8 @@ __global__ __launch_bounds__(RB) void rollout_persistent_kernel(RollArgs a, cons
     // sample + env step on every row (split angle functions); row 0 stores
     double rew = 0.0;
     bool done = false;
-    sample_and_step<ENV, true, true>(a, row, z, sdv, zn, s, rew, done, valid && g == 0, g, capr);
+    if constexpr (EV) mode_and_step<ENV, true, true>(a, row, z, sdv, s, rew, done, valid && g == 0, g, capr);
+    else sample_and_step<ENV, true, true>(a, row, z, sdv, zn, s, rew, done, valid && g == 0, g, capr);
     PSTAMP(t, 4);
     // episode bookkeeping on every row, so the rows keep identical env state
     // (finish_env_step: gym TimeLimit => terminated; limit / horizon cut => not)
@@ -1021,6 +1071,7 @@ __global__ __launch_bounds__(RB) void rollout_persistent_kernel(RollArgs a, cons
         ept += 1;
       }
     }
+    if constexpr (EV) continue;  // nothing to hand on
     if (valid && g == 0) {
       double o[O];
       EC::obs(s, o);
@@ -1047,6 +1098,7 @@ __global__ __launch_bounds__(RB) void rollout_persistent_kernel(RollArgs a, cons
     a.b.env_int[e] = ept;
     a.b.env_int[E + e] = (int32_t)epc;
   }
+  if constexpr (EV) return;  // the filter state stays as it was
   if (blockIdx.x == 0 && kcol && jj == 0) {
     double* fs_out = a.b.filter_state + (T & 1) * a.FS;
     if (k == 0) fs_out[0] = fn;
@@ -1064,6 +1116,39 @@ __global__ __launch_bounds__(RB) void rollout_persistent_kernel(RollArgs a, cons
   }
 }
 
+#ifdef MRL_ROLLOUT_EVAL_UNIT
+// The evaluation unit (rollout_eval.hip compiles this file with MRL_ROLLOUT_EVAL_UNIT): the EV
+// instantiations of the three kernels above behind the launchers the entry points below call.
+// They are a unit of their own because instantiated here, beside the training kernels, they
+// changed a training kernel's listing (Swimmer's step kernel, a loop branch in its other
+// sense: the envs' step functions gain callers in the module); this unit's device code holds
+// the EV kernels alone, and this file's the kernels it held before.
+void launch_rollout_reset_eval(const RollArgs& a, hipStream_t s) {
+  dispatch_thread_env(a.d.env_id, [&](auto env) {
+    hipLaunchKernelGGL((rollout_reset_kernel<env(), true>), dim3(a.nb), dim3(RB), 0, s, a);
+  });
+}
+void launch_rollout_step_eval(const RollArgs& a, bool bf, const float* logstd, const float* rimage, int t,
+                              hipStream_t s) {
+  dispatch_thread_env(a.d.env_id, [&](auto env) {
+    dispatch_bool(bf, [&](auto BF) {
+      hipLaunchKernelGGL((rollout_step_kernel<env(), BF(), true>), dim3(a.nb), dim3(RB), 0, s, a, logstd, rimage, t);
+    });
+  });
+}
+// independent blocks: no workspace, no residency check, no stamps
+void launch_rollout_persistent_eval(const RollArgs& a, bool bf, const float* logstd, const float* rimage,
+                                    hipStream_t s) {
+  dispatch_thread_env(a.d.env_id, [&](auto env) {
+    dispatch_bool(bf, [&](auto BF) {
+      hipLaunchKernelGGL((rollout_persistent_kernel<env(), BF(), false, true>), dim3(a.nb), dim3(RB), 0, s, a, logstd,
+                         rimage, nullptr);
+    });
+  });
+}
+
+}  // namespace mrl
+#else
 __global__ void rollout_finish_kernel(RollArgs a, int O) {
   const int D = O + 1, T = a.d.horizon;
   const double* fs_in = a.b.filter_state + (T & 1) * a.FS;
@@ -1122,6 +1207,7 @@ int64_t mrl_record_doubles(int32_t env_id) { return filt_doubles(env_info(env_id
 int64_t mrl_rollout_blocks(int32_t n_envs) { return env_blocks(n_envs); }
 int64_t mrl_rollout_noise_doubles(const mrl_rollout_desc* d) {
   if (!d || d->n_envs <= 0 || d->horizon <= 0) return -1;
+  if (roll_eval(d)) return 0;  // the head's mode: no noise is drawn
   const EnvInfo ei = env_info(d->env_id);
   return (int64_t)d->horizon * d->n_envs * (ei.discrete ? 1 : ei.act);
 }
@@ -1130,6 +1216,7 @@ int mrl_rollout_noise(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, doub
   int rc = check_roll(d, b);
   if (rc) return rc;
   if (!out) return fail(E_ARG, "null noise rows");
+  if (roll_eval(d)) return fail(E_ARG, "mrl_rollout_noise: MRL_ROLLOUT_EVAL draws no noise");
   RollArgs a = make_args(d, b);
   const EnvInfo ei = env_info(d->env_id);
   const int64_t per_step = (int64_t)d->n_envs * (ei.discrete ? 1 : (ei.act + 1) / 2);
@@ -1143,7 +1230,8 @@ int mrl_rollout_reset(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, void
   if (rc) return rc;
   if (d->env_id == MRL_ENV_HUMANOID) return fail(E_UNSUPPORTED, "Humanoid runs on the layered rollout (mrl_rollout_reset_rows)");
   RollArgs a = make_args(d, b);
-  MRL_DISPATCH_THREAD_ENV(d->env_id, rollout_reset_kernel, dim3(a.nb), dim3(RB), 0, (hipStream_t)stream, a);
+  if (roll_eval(d)) launch_rollout_reset_eval(a, (hipStream_t)stream);
+  else MRL_DISPATCH_THREAD_ENV(d->env_id, rollout_reset_kernel, dim3(a.nb), dim3(RB), 0, (hipStream_t)stream, a);
   return hip_check(hipGetLastError(), "mrl_rollout_reset");
 }
 
@@ -1161,7 +1249,7 @@ int mrl_rollout_pack(const mrl_rollout_desc* d, const mrl_mlp_desc* pol, const f
   const RDims r = rollout_dims(pol->n_in);
   const MlpDims md = mlp_dims(pol->n_in, pol->n_out, pol->head == MRL_HEAD_GAUSS);
   hipLaunchKernelGGL(rollout_pack_kernel, dim3((r.size + 255) / 256), dim3(256), 0, (hipStream_t)stream, r, md, theta,
-                     rimage, (int)(d->compute == MRL_COMPUTE_BF16));
+                     rimage, (int)(roll_compute(d) == MRL_COMPUTE_BF16));
   return hip_check(hipGetLastError(), "mrl_rollout_pack");
 }
 
@@ -1209,13 +1297,18 @@ int mrl_rollout_run(const mrl_rollout_desc* d, const mrl_mlp_desc* pol, const fl
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   RollArgs a = make_args(d, b);
+  const MlpDims md = mlp_dims(pol->n_in, pol->n_out, pol->head == MRL_HEAD_GAUSS);
+  const float* logstd = pol->head == MRL_HEAD_GAUSS ? theta + md.tls : nullptr;
+  const bool bf = roll_compute(d) == MRL_COMPUTE_BF16, st = b->stamps != nullptr;
+  if (roll_eval(d) && persistent) {
+    launch_rollout_persistent_eval(a, bf, logstd, rimage, s);
+    return hip_check(hipGetLastError(), "mrl_rollout_run");
+  }
   if (!persistent || !sync || !persistent_fits(a.nb, s, d->launch_cus)) {
     rc = mrl_rollout_reset(d, b, stream);
     for (int32_t t = 0; t < d->horizon && rc == OK; ++t) rc = mrl_rollout_step(d, pol, theta, rimage, b, t, stream);
     return rc;
   }
-  const MlpDims md = mlp_dims(pol->n_in, pol->n_out, pol->head == MRL_HEAD_GAUSS);
-  const float* logstd = pol->head == MRL_HEAD_GAUSS ? theta + md.tls : nullptr;
   {
     const int64_t n16 = mrl_rollout_sync_bytes(d) / 16;  // SYNC_HEAD_BYTES + 16-B granules
     const int nblk = (int)std::min<int64_t>((n16 + 255) / 256, 256);
@@ -1226,7 +1319,6 @@ int mrl_rollout_run(const mrl_rollout_desc* d, const mrl_mlp_desc* pol, const fl
   // on their own), and the step hand-off polls are bounded (SPIN_LIMIT).  A cooperative
   // launch made HIP keep a runtime-owned queue that its teardown destroyed after an
   // attached rocprofv3 had finalised: the profiled process crashed at exit.
-  const bool bf = d->compute == MRL_COMPUTE_BF16, st = b->stamps != nullptr;
   dispatch_thread_env(d->env_id, [&](auto env) {
     dispatch_bool(bf, [&](auto BF) {
       dispatch_bool(st, [&](auto ST) {
@@ -1246,8 +1338,12 @@ int mrl_rollout_step(const mrl_rollout_desc* d, const mrl_mlp_desc* pol, const f
   RollArgs a = make_args(d, b);
   const MlpDims md = mlp_dims(pol->n_in, pol->n_out, pol->head == MRL_HEAD_GAUSS);
   const float* logstd = pol->head == MRL_HEAD_GAUSS ? theta + md.tls : nullptr;
-  const bool bf = d->compute == MRL_COMPUTE_BF16;
+  const bool bf = roll_compute(d) == MRL_COMPUTE_BF16;
   hipStream_t s = (hipStream_t)stream;
+  if (roll_eval(d)) {
+    launch_rollout_step_eval(a, bf, logstd, rimage, t, s);
+    return hip_check(hipGetLastError(), "mrl_rollout_step");
+  }
   dispatch_thread_env(d->env_id, [&](auto env) {
     dispatch_bool(bf, [&](auto BF) {
       hipLaunchKernelGGL((rollout_step_kernel<env(), BF()>), dim3(a.nb), dim3(RB), 0, s, a, logstd, rimage, t);
@@ -1259,9 +1355,11 @@ int mrl_rollout_step(const mrl_rollout_desc* d, const mrl_mlp_desc* pol, const f
 int mrl_rollout_finish(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, void* stream) {
   int rc = check_roll(d, b);
   if (rc) return rc;
+  if (roll_eval(d)) return OK;  // no reward partial to fold, and the noise's step base stays
   RollArgs a = make_args(d, b);
   hipLaunchKernelGGL(rollout_finish_kernel, dim3(1), dim3(RB), 0, (hipStream_t)stream, a, env_info(d->env_id).obs);
   return hip_check(hipGetLastError(), "mrl_rollout_finish");
 }
 
 }  // extern "C"
+#endif  // MRL_ROLLOUT_EVAL_UNIT

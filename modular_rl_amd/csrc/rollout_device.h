@@ -274,6 +274,70 @@ __device__ inline void sample_and_step(const RollArgs& a, int64_t row, const flo
   }
 }
 
+// ------------------------------------------------------------------ evaluation mode
+// MRL_ROLLOUT_EVAL (mrl_hip.h): the kernels' EV instantiations.  Its own text, beside
+// sample_and_step rather than folded into it (§3's Box-Muller note: a shared helper has changed
+// the existing listings before).
+//
+// column k of the frozen observation filter: what mrl_pop_rollout feeds its policies -- the
+// state's mean and sqrt(S / (n - 1)) + 1e-8, or with fewer than two observations mean 0 and
+// denominator 1, which leave the observation bit for bit (the caller clips at +-5)
+__device__ inline void frozen_filter_column(const double* fs, int D, int k, double& mean, double& den) {
+  const double n = fs[0];
+  mean = 0.0;
+  den = 1.0;
+  if (n >= 2.0) {
+    mean = fs[2 + k];
+    den = sqrt(fs[2 + D + k] / (n - 1.0)) + 1e-8;
+  }
+}
+
+// sample_and_step with the head's mode for the action (ProbType.maxprob; core.py:261-267 with
+// stochastic = False): the Gauss mean, or the arg-max logit with the lowest index on a tie
+// (np.argmax).  No noise row is read; act / prob rows as sample_and_step writes them.
+template <int ENV, bool QUAD = false, bool SD = false>
+__device__ inline void mode_and_step(const RollArgs& a, int64_t row, const float* z, const float* logstd, double* s,
+                                     double& rew, bool& done, bool store = true, int h = 0,
+                                     const double* capc = nullptr) {
+  using EC = EnvC<ENV>;
+  constexpr int A = EC::ACT;
+  if constexpr (EC::DISCRETE) {
+    float m = z[0];
+    int act = 0;
+#pragma unroll
+    for (int q = 1; q < A; ++q)
+      if (z[q] > m) {
+        m = z[q];
+        act = q;
+      }
+    float p[A], se = 0.f;
+#pragma unroll
+    for (int q = 0; q < A; ++q) {
+      p[q] = expf(z[q] - m);
+      se += p[q];
+    }
+    if (store) {
+      reinterpret_cast<int32_t*>(a.b.act)[row] = act;
+#pragma unroll
+      for (int q = 0; q < A; ++q) a.b.prob[row * A + q] = p[q] / se;
+    }
+    EC::step(s, act, rew, done);
+  } else {
+    float av[A];
+#pragma unroll
+    for (int q = 0; q < A; ++q) {
+      av[q] = z[q];
+      if (store) {
+        reinterpret_cast<float*>(a.b.act)[row * A + q] = z[q];
+        a.b.prob[row * 2 * A + q] = z[q];
+        a.b.prob[row * 2 * A + A + q] = SD ? logstd[q] : expf(logstd[q]);
+      }
+    }
+    if constexpr (QUAD) EC::step_cont_quad(s, av, rew, done, h, capc);
+    else EC::step(s, av, rew, done);
+  }
+}
+
 // episode bookkeeping: gym TimeLimit => done (terminated, bootstrap 0); the rollout
 // loop limit / horizon cut => not terminated (core.py:190-207, 73); auto-reset; store
 template <int ENV>

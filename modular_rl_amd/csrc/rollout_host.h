@@ -12,12 +12,26 @@
 
 namespace mrl {
 
+// desc.compute: the policy net's dtype, and the evaluation flag beside it (MRL_ROLLOUT_EVAL)
+inline int roll_compute(const mrl_rollout_desc* d) { return d->compute & ~MRL_ROLLOUT_EVAL; }
+inline bool roll_eval(const mrl_rollout_desc* d) { return (d->compute & MRL_ROLLOUT_EVAL) != 0; }
+
 inline int check_roll(const mrl_rollout_desc* d, const mrl_rollout_bufs* b) {
   if (!d || !b) return fail(E_ARG, "null desc/bufs");
   if (!env_known(d->env_id)) return fail(E_UNSUPPORTED, "unknown env_id");
   if (d->n_envs <= 0 || d->horizon <= 0 || d->timestep_limit <= 0) return fail(E_ARG, "bad sizes");
-  if (d->compute != MRL_COMPUTE_F32 && d->compute != MRL_COMPUTE_BF16) return fail(E_ARG, "bad compute");
+  if (roll_compute(d) != MRL_COMPUTE_F32 && roll_compute(d) != MRL_COMPUTE_BF16) return fail(E_ARG, "bad compute");
   if (!b->env_state || !b->env_int || !b->filter_state || !b->records || !b->iteration) return fail(E_ARG, "null state");
+  return OK;
+}
+
+// the sampling-noise rows of a step: required in training, refused in evaluation, which draws none
+inline int check_noise(const mrl_rollout_desc* d, const mrl_rollout_bufs* b) {
+  if (roll_eval(d)) {
+    if (b->noise) return fail(E_ARG, "bufs.noise: MRL_ROLLOUT_EVAL takes the head's mode and reads no noise rows");
+    return OK;
+  }
+  if (!b->noise) return fail(E_ARG, "bufs.noise: sampling-noise rows (mrl_rollout_noise or injected) required");
   return OK;
 }
 
@@ -51,7 +65,8 @@ inline int check_fused_run(const mrl_rollout_desc* d, const mrl_mlp_desc* pol, c
   if (!pol || !theta || !rimage) return fail(E_ARG, "null policy");
   if (d->env_id == MRL_ENV_HUMANOID) return fail(E_UNSUPPORTED, "Humanoid runs on the layered rollout");
   if (!b->obs || !b->act || !b->prob || !b->rew || !b->flags || !b->ep_t) return fail(E_ARG, "null trajectory buffer");
-  if (!b->noise) return fail(E_ARG, "bufs.noise: sampling-noise rows (mrl_rollout_noise or injected) required");
+  rc = check_noise(d, b);
+  if (rc) return rc;
   return check_fused_policy(d, pol);
 }
 
@@ -132,5 +147,18 @@ inline size_t hm_lds_bytes(int wpb, int n_envs) { return wpb == 1 ? hm_lds_pad(n
 // hm_env_reset_kernel / hm_env_step_kernel (rollout_layered.hip) for mrl_env_reset / mrl_env_step
 void launch_hm_env_reset(const RollArgs& a, const mrl_env_io& io, hipStream_t s);
 void launch_hm_env_step(const RollArgs& a, const mrl_env_io& io, int auto_reset, hipStream_t s);
+
+// The evaluation instantiations (MRL_ROLLOUT_EVAL) of the rollout kernels, compiled in units of
+// their own -- rollout_eval.hip and rollout_layered_eval.hip -- for the entry points of
+// rollout.hip and rollout_layered.hip, which have checked the arguments.
+void launch_rollout_reset_eval(const RollArgs& a, hipStream_t s);
+void launch_rollout_step_eval(const RollArgs& a, bool bf, const float* logstd, const float* rimage, int t,
+                              hipStream_t s);
+void launch_rollout_persistent_eval(const RollArgs& a, bool bf, const float* logstd, const float* rimage,
+                                    hipStream_t s);
+struct HeadRows;
+void launch_lrollout_obs_eval(const RollArgs& a, int t, hipStream_t s);
+void launch_lrollout_act_eval(const RollArgs& a, const float* z, const HeadRows& hr, const float* logstd, int t,
+                              hipStream_t s);
 
 }  // namespace mrl

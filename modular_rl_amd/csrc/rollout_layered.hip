@@ -10,6 +10,7 @@
 
 namespace mrl {
 
+#ifndef MRL_ROLLOUT_EVAL_UNIT
 // per-(env block, column chunk) two-pass partial of the SoA rows raw[k][e0 .. e0+nvalid):
 // column k = 32*blockIdx.y + (tid & 31); 8 thread groups stride the envs.
 __global__ __launch_bounds__(RB) void lrollout_partials_kernel(RollArgs a, int D, int rec_parity, int with_rew) {
@@ -32,6 +33,7 @@ __global__ __launch_bounds__(RB) void lrollout_partials_kernel(RollArgs a, int D
     r[1] = with_rew ? (double)nvalid : 0.0;
   }
 }
+#endif  // MRL_ROLLOUT_EVAL_UNIT
 
 template <int ENV>
 __global__ __launch_bounds__(RB) void lrollout_reset_kernel(RollArgs a) {
@@ -52,8 +54,11 @@ __global__ __launch_bounds__(RB) void lrollout_reset_kernel(RollArgs a) {
 
 // merge of the batch records (block order, two passes: n, mean = sum n_b m_b / n,
 // M2 = sum M2_b + n_b (m_b - mean)^2 -- oracle/rollout_np.py _batch) into the running
-// stat, then the normalised obs rows of step t for this (env block, column chunk)
-template <int ENV>
+// stat, then the normalised obs rows of step t for this (env block, column chunk).
+// EV (here, in lrollout_act_kernel and in hm_act_kernel): the evaluation instantiation
+// (MRL_ROLLOUT_EVAL, rollout_device.h) -- here the frozen filter: no record is read, nothing
+// is merged, the state is not written
+template <int ENV, bool EV = false>
 __global__ __launch_bounds__(RB) void lrollout_obs_kernel(RollArgs a, int t) {
   using EC = EnvC<ENV>;
   constexpr int O = EC::OBS, D = O + 1;
@@ -77,7 +82,10 @@ __global__ __launch_bounds__(RB) void lrollout_obs_kernel(RollArgs a, int t) {
     const int k = kbase + kb + G * q;
     v[q] = (k < O && el < nvalid) ? a.b.raw_obs[(int64_t)k * E + e0 + el] : 0.0;
   }
-  if (threadIdx.x < LCOLS && kbase + (int)threadIdx.x < D) {
+  if constexpr (EV) {
+    if (threadIdx.x < LCOLS && kbase + (int)threadIdx.x < O)
+      frozen_filter_column(a.b.filter_state, D, kbase + threadIdx.x, fmean[threadIdx.x], fden[threadIdx.x]);
+  } else if (threadIdx.x < LCOLS && kbase + (int)threadIdx.x < D) {
     const int k = kbase + threadIdx.x;
     const bool isr = (k == O);
     double n, M, S;
@@ -129,7 +137,7 @@ __global__ __launch_bounds__(RB) void lrollout_obs_kernel(RollArgs a, int t) {
 }
 
 // sample + env step + raw next obs / reward (SoA) for one env per thread
-template <int ENV>
+template <int ENV, bool EV = false>
 __global__ __launch_bounds__(RB) void lrollout_act_kernel(RollArgs a, const float* __restrict__ zrows,
                                                           const float* __restrict__ logstd, int t) {
   using EC = EnvC<ENV>;
@@ -145,10 +153,11 @@ __global__ __launch_bounds__(RB) void lrollout_act_kernel(RollArgs a, const floa
 #pragma unroll
   for (int q = 0; q < A; ++q) z[q] = zrows[(int64_t)e * A + q];
   double zn[A + 1];
-  load_noise<ENV>(a, row, zn);
+  if constexpr (!EV) load_noise<ENV>(a, row, zn);
   double rew = 0.0;
   bool done = false;
-  sample_and_step<ENV>(a, row, z, logstd, zn, s, rew, done);
+  if constexpr (EV) mode_and_step<ENV>(a, row, z, logstd, s, rew, done);
+  else sample_and_step<ENV>(a, row, z, logstd, zn, s, rew, done);
   finish_env_step<ENV>(a, e, row, t, s, rew, done);
   double* raw = a.b.raw_obs;
   EC::obs_out(s, [&](int k, double v) { raw[(int64_t)k * E + e] = v; });
@@ -279,7 +288,7 @@ __device__ inline float head_z(const HeadRows& hr, int e, int lane) {
   return z;
 }
 
-template <int WPB>
+template <int WPB, bool EV = false>
 __global__ __launch_bounds__(64 * WPB) void hm_act_kernel(RollArgs a, const float* __restrict__ zrows, HeadRows hr,
                                                           const float* __restrict__ logstd, int t) {
   __shared__ hm::Shared S;
@@ -327,8 +336,11 @@ __global__ __launch_bounds__(64 * WPB) void hm_act_kernel(RollArgs a, const floa
   if (lane < A) {
     const float z = fused ? zh : zrows[(int64_t)e * A + lane];
     const float sd = expf(logstd[lane]);
-    const double zn = reinterpret_cast<const double*>(a.b.noise)[row * A + lane];
-    const float av = __fadd_rn(__fmul_rn((float)zn, sd), z);
+    float av = z;  // EV: the mean, no noise row is read
+    if constexpr (!EV) {
+      const double zn = reinterpret_cast<const double*>(a.b.noise)[row * A + lane];
+      av = __fadd_rn(__fmul_rn((float)zn, sd), z);
+    }
     reinterpret_cast<float*>(a.b.act)[row * A + lane] = av;
     a.b.prob[row * 2 * A + lane] = z;
     a.b.prob[row * 2 * A + A + lane] = sd;
@@ -481,6 +493,36 @@ __global__ __launch_bounds__(64 * WPB) void hm_env_step_kernel(RollArgs a, mrl_e
   hm::save_kcache(W, kc, lane);  // W holds forward() of the state just stored
 }
 
+#ifdef MRL_ROLLOUT_EVAL_UNIT
+// The evaluation unit (rollout_layered_eval.hip compiles this file with MRL_ROLLOUT_EVAL_UNIT):
+// the EV instantiations of lrollout_obs_kernel, lrollout_act_kernel and hm_act_kernel behind
+// the launchers the entry points below call -- a unit of their own for rollout.hip's reason
+// (its launchers): the training kernels' unit holds the kernels it held before.  No partials
+// launch follows an evaluation step: there is nothing to merge.
+void launch_lrollout_obs_eval(const RollArgs& a, int t, hipStream_t s) {
+  const dim3 grid(a.nb, (env_info(a.d.env_id).obs + 1 + LCOLS - 1) / LCOLS);
+  dispatch_env(a.d.env_id, [&](auto env) {
+    hipLaunchKernelGGL((lrollout_obs_kernel<env(), true>), grid, dim3(RB), 0, s, a, t);
+  });
+}
+void launch_lrollout_act_eval(const RollArgs& a, const float* z, const HeadRows& hr, const float* logstd, int t,
+                              hipStream_t s) {
+  const int E = a.d.n_envs;
+  if (a.d.env_id == MRL_ENV_HUMANOID) {
+    const int wpb = hm_wpb();
+    const dim3 grid((E + wpb - 1) / wpb), block(64 * wpb);
+    const size_t lds = hm_lds_bytes(wpb, E);
+    if (wpb == 4) hipLaunchKernelGGL((hm_act_kernel<4, true>), grid, block, lds, s, a, z, hr, logstd, t);
+    else hipLaunchKernelGGL((hm_act_kernel<1, true>), grid, block, lds, s, a, z, hr, logstd, t);
+    return;
+  }
+  dispatch_thread_env(a.d.env_id, [&](auto env) {
+    hipLaunchKernelGGL((lrollout_act_kernel<env(), true>), dim3((E + 63) / 64), dim3(64), 0, s, a, z, logstd, t);
+  });
+}
+
+}  // namespace mrl
+#else
 void launch_hm_env_reset(const RollArgs& a, const mrl_env_io& io, hipStream_t s) {
   MRL_LAUNCH_HM(hm_env_reset_kernel, hm_lds_state, a.d.n_envs, s, a, io);
 }
@@ -512,7 +554,8 @@ int mrl_rollout_reset_rows(const mrl_rollout_desc* d, const mrl_rollout_bufs* b,
   hipStream_t s = (hipStream_t)stream;
   if (d->env_id == MRL_ENV_HUMANOID) MRL_LAUNCH_HM(hm_reset_kernel, hm_lds_state, d->n_envs, s, a);
   else MRL_DISPATCH_THREAD_ENV(d->env_id, lrollout_reset_kernel, genv, dim3(64), 0, s, a);
-  hipLaunchKernelGGL(lrollout_partials_kernel, gpart, dim3(RB), 0, s, a, D, 0, 0);
+  // evaluation: the reset kernels as they are (raw_obs feeds the obs kernel), no partial of obs_0
+  if (!roll_eval(d)) hipLaunchKernelGGL(lrollout_partials_kernel, gpart, dim3(RB), 0, s, a, D, 0, 0);
   return hip_check(hipGetLastError(), "mrl_rollout_reset_rows");
 }
 
@@ -523,7 +566,8 @@ int mrl_rollout_obs(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, int32_
   if (t < 0 || t >= d->horizon) return fail(E_ARG, "t out of range");
   RollArgs a = make_args(d, b);
   const dim3 grid(a.nb, (env_info(d->env_id).obs + 1 + LCOLS - 1) / LCOLS);
-  MRL_DISPATCH_ENV(d->env_id, lrollout_obs_kernel, grid, dim3(RB), 0, (hipStream_t)stream, a, t);
+  if (roll_eval(d)) launch_lrollout_obs_eval(a, t, (hipStream_t)stream);
+  else MRL_DISPATCH_ENV(d->env_id, lrollout_obs_kernel, grid, dim3(RB), 0, (hipStream_t)stream, a, t);
   return hip_check(hipGetLastError(), "mrl_rollout_obs");
 }
 
@@ -535,7 +579,8 @@ static int rollout_act(const mrl_rollout_desc* d, int32_t head, int32_t n_out, c
     return fail(E_ARG, "null trajectory buffer");
   if ((hr.hid || hr.hid16) && d->env_id != MRL_ENV_HUMANOID)
     return fail(E_UNSUPPORTED, "the fused head is the Humanoid step's");
-  if (!b->noise) return fail(E_ARG, "bufs.noise: sampling-noise rows (mrl_rollout_noise or injected) required");
+  rc = check_noise(d, b);
+  if (rc) return rc;
   EnvInfo ei = env_info(d->env_id);
   const bool gauss = head == MRL_HEAD_GAUSS;
   if (n_out != ei.act || gauss == (bool)ei.discrete || (!gauss && head != MRL_HEAD_SOFTMAX))
@@ -546,6 +591,10 @@ static int rollout_act(const mrl_rollout_desc* d, int32_t head, int32_t n_out, c
   const int D = ei.obs + 1;
   const dim3 genv((d->n_envs + 63) / 64), gpart(a.nb, (D + LCOLS - 1) / LCOLS);
   hipStream_t s = (hipStream_t)stream;
+  if (roll_eval(d)) {
+    launch_lrollout_act_eval(a, z, hr, logstd, t, s);
+    return hip_check(hipGetLastError(), "mrl_rollout_act");
+  }
   if (d->env_id == MRL_ENV_HUMANOID) MRL_LAUNCH_HM(hm_act_kernel, hm_lds_bytes, d->n_envs, s, a, z, hr, logstd, t);
   else MRL_DISPATCH_THREAD_ENV(d->env_id, lrollout_act_kernel, genv, dim3(64), 0, s, a, z, logstd, t);
   hipLaunchKernelGGL(lrollout_partials_kernel, gpart, dim3(RB), 0, s, a, D, (t + 1) & 1, 1);
@@ -565,7 +614,7 @@ int mrl_rollout_act_head(const mrl_rollout_desc* d, int32_t head, int32_t n_out,
   if (d->env_id != MRL_ENV_HUMANOID || n_out != HM_ACT)
     return fail(E_UNSUPPORTED, "mrl_rollout_act_head: the fused head is the Humanoid step's (17 outputs)");
   return rollout_act(d, head, n_out, nullptr,
-                     HeadRows{hidden, w_head, b_head, n_hidden, (int)(d->compute == MRL_COMPUTE_BF16), nullptr}, logstd,
+                     HeadRows{hidden, w_head, b_head, n_hidden, (int)(roll_compute(d) == MRL_COMPUTE_BF16), nullptr}, logstd,
                      b, t, stream);
 }
 
@@ -576,9 +625,10 @@ int mrl_rollout_act_head_bf16(const mrl_rollout_desc* d, int32_t head, int32_t n
     return fail(E_ARG, "mrl_rollout_act_head_bf16: bad arguments");
   if (d->env_id != MRL_ENV_HUMANOID || n_out != HM_ACT)
     return fail(E_UNSUPPORTED, "mrl_rollout_act_head_bf16: the fused head is the Humanoid step's (17 outputs)");
-  if (d->compute != MRL_COMPUTE_BF16) return fail(E_ARG, "mrl_rollout_act_head_bf16: bf16 hidden rows need MRL_COMPUTE_BF16");
+  if (roll_compute(d) != MRL_COMPUTE_BF16) return fail(E_ARG, "mrl_rollout_act_head_bf16: bf16 hidden rows need MRL_COMPUTE_BF16");
   return rollout_act(d, head, n_out, nullptr, HeadRows{nullptr, w_head, b_head, n_hidden, 1, hidden16}, logstd, b, t,
                      stream);
 }
 
 }  // extern "C"
+#endif  // MRL_ROLLOUT_EVAL_UNIT
