@@ -8,7 +8,7 @@ SRCS := $(CSRC)/mlp_kernels.hip $(CSRC)/mlp_rows_vjp.hip $(CSRC)/mlp_vjp16.hip $
   $(CSRC)/rollout_eval.hip $(CSRC)/rollout_layered_eval.hip \
   $(CSRC)/env_api.hip $(CSRC)/gemm.hip $(CSRC)/gemm_bf16.hip $(CSRC)/gemm_bf16_big.hip \
   $(CSRC)/gemm_bf16_stream.hip $(CSRC)/gemm_bf16_tn.hip $(CSRC)/cem.hip \
-  $(CSRC)/pop_rollout.hip $(CSRC)/pop_rollout_small.hip $(CSRC)/runtime.hip
+  $(CSRC)/pop_rollout.hip $(CSRC)/pop_rollout_small.hip $(CSRC)/pop_rollout_humanoid.hip $(CSRC)/runtime.hip
 HDRS := $(wildcard $(CSRC)/*.h) include/mrl_hip.h
 OBJS := $(patsubst $(CSRC)/%.hip,build/%.o,$(SRCS))
 LIB := modular_rl_amd/libmrl_hip.so

@@ -640,7 +640,7 @@ typedef struct {
  * MountainCar, Acrobot, InvertedPendulum, InvertedDoublePendulum, Reacher, Swimmer, HalfCheetah)
  * with its 64-64 policy net;
  * anything else is MRL_E_UNSUPPORTED here -- smaller nets (the reference's CEM battery runs
- * hid_sizes 10,5) go through mrl_pop_rollout_mlp below. */
+ * hid_sizes 10,5) go through mrl_pop_rollout_mlp below, Humanoid through mrl_pop_rollout_wave. */
 int mrl_pop_rollout(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, const mrl_mlp_desc* pol,
                     const float* thetas, int64_t ld_theta, const double* filter_state,
                     const mrl_pop_io* io, void* stream);
@@ -648,22 +648,48 @@ int mrl_pop_rollout(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, const 
 /* The same rollout for a small net: the tanh MLP obs -> hid_sizes[0] -> ... -> act of env_id
  * with the env's head (softmax | Gauss), n_hid hidden layers (0: the linear policy x W + b).
  * A block keeps the forward parameters of its 64 candidates in LDS for the whole episode, so
- * the shape must fit: mrl_pop_rollout_mlp_fits, 1 or 0 (Humanoid, n_hid > 3, a width outside
- * [1, 64] and a population tile beyond one block's LDS are 0), negative on bad arguments.
+ * the shape must fit: mrl_pop_rollout_mlp_fits, 1 or 0 (Humanoid -- a wave per candidate,
+ * mrl_pop_rollout_wave below --, n_hid > 3, a width outside [1, 64] and a population tile
+ * beyond one block's LDS are 0), negative on bad arguments.
  * mrl_pop_mlp_num_params: the length of one theta in flat Keras order (W0, b0, ..., logstd
  * included for a Gauss head), negative on bad arguments (unknown env, n_hid < 0, null hid_sizes
  * with n_hid > 0, a width < 1).
  * mrl_pop_rollout_mlp: everything mrl_pop_rollout documents -- reset stream and counter, frozen
  * filter, deterministic action, end of episode, ld_theta == 0, the outputs and the trace,
  * env_state / env_int -- with the same arithmetic: per unit an fmaf chain over the inputs in
- * ascending order from 0, plus the bias, tanhf on hidden layers.  A shape that does not fit is
- * MRL_E_UNSUPPORTED. */
+ * ascending order from 0, plus the bias, tanhf on hidden layers.  A shape that does not fit,
+ * and Humanoid (mrl_pop_rollout_wave), is MRL_E_UNSUPPORTED. */
 int64_t mrl_pop_mlp_num_params(int32_t env_id, const int32_t* hid_sizes, int32_t n_hid);
 int32_t mrl_pop_rollout_mlp_fits(int32_t env_id, const int32_t* hid_sizes, int32_t n_hid);
 int mrl_pop_rollout_mlp(const mrl_rollout_desc* d, const mrl_rollout_bufs* b,
                         const int32_t* hid_sizes, int32_t n_hid,
                         const float* thetas, int64_t ld_theta, const double* filter_state,
                         const mrl_pop_io* io, void* stream);
+
+/* The same rollout for the wave-per-env envs -- Humanoid-v2 -- with one wave per candidate: the
+ * wave keeps its env's state in LDS and runs the whole episode (reset, then per step
+ * observation, Welford partial, frozen filter, policy forward, FRAME_SKIP substeps, reward).
+ * The policy is the tanh MLP 376 -> hid_sizes[0] -> ... -> 17 with the Gauss head (the action
+ * is the mean), n_hid <= 3 hidden layers of 1 .. 64 units, theta in mrl_pop_mlp_num_params'
+ * layout (3944 floats for hid_sizes 10,5) and read from memory every step.
+ * mrl_pop_rollout_wave_fits: 1 for Humanoid with such a shape, 0 for every other known env and
+ * every other shape, MRL_E_ARG for an unknown env, n_hid < 0 or null hid_sizes with n_hid > 0.
+ * mrl_pop_rollout_wave: everything mrl_pop_rollout documents -- reset stream and counter (a
+ * VecEnv of the same seed replays a traced call bit for bit), frozen filter, end of episode,
+ * ld_theta == 0, the outputs (stat is [N, 1 + 2*376]) and the trace, env_state (the state rows
+ * and their kinematics cache, mrl_env_state_doubles) / env_int -- and the argument checks of
+ * mrl_pop_rollout_mlp; another env or a shape _fits turns away is MRL_E_UNSUPPORTED.
+ * Arithmetic: f32 fmaf products; the first layer's 376 inputs are spread over the lanes (lane l
+ * takes inputs l, l + 64, ... in ascending order, one accumulator per output) and the 64
+ * partials of an output are summed by the xor butterfly (offsets 32, 16, 8, 4, 2, 1), then the
+ * bias; later layers are one fmaf chain per output over the inputs in ascending order, then
+ * the bias; tanhf on hidden layers.  The order is fixed: the same inputs give the same bits on
+ * every call, and a shared theta (ld_theta == 0) the bits of N copies. */
+int32_t mrl_pop_rollout_wave_fits(int32_t env_id, const int32_t* hid_sizes, int32_t n_hid);
+int mrl_pop_rollout_wave(const mrl_rollout_desc* d, const mrl_rollout_bufs* b,
+                         const int32_t* hid_sizes, int32_t n_hid,
+                         const float* thetas, int64_t ld_theta, const double* filter_state,
+                         const mrl_pop_io* io, void* stream);
 
 /* thetas[i, p] = (float)(mean[p] + sample_std[p] * z(i, p)), product and sum in fp64 (cem.py:42);
  * z: Box-Muller (as the rollout's sampling noise) of Philox (seed, domain 2, gid i, word

@@ -88,6 +88,12 @@ class PopIO(ctypes.Structure):
                 ("trace_act", vp), ("trace_rew", vp)]
 
 
+def predicate(v):
+    """restype of an int32 predicate (1 / 0, negative on bad arguments): a callable restype reads
+    a C int; unlike a status, its 0 is an answer, not a success that null arguments must not get."""
+    return int(v)
+
+
 # name -> (restype, argtypes); every symbol include/mrl_hip.h declares
 SIGNATURES = {
     "mrl_last_error": (ctypes.c_char_p, []),
@@ -184,6 +190,8 @@ SIGNATURES = {
     "mrl_pop_mlp_num_params": (i64, [i32, vp, i32]),
     "mrl_pop_rollout_mlp_fits": (i32, [i32, vp, i32]),
     "mrl_pop_rollout_mlp": (i32, [vp, vp, vp, i32, vp, i64, vp, vp, vp]),
+    "mrl_pop_rollout_wave_fits": (predicate, [i32, vp, i32]),
+    "mrl_pop_rollout_wave": (i32, [vp, vp, vp, i32, vp, i64, vp, vp, vp]),
     "mrl_cem_sample": (i32, [vp, vp, i64, i64, ctypes.c_uint64, ctypes.c_uint64, vp, i64, vp]),
     "mrl_cem_refit_workspace_bytes": (ctypes.c_size_t, [i64, i64]),
     "mrl_cem_refit": (i32, [vp, i64, i64, i64, vp, i32, vp, vp, vp, vp, vp]),

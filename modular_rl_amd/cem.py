@@ -13,7 +13,8 @@ the host sees ``ys`` and the two ``[P]`` vectors per generation.
 ``run_cem_algorithm`` is the reference's driver (`cem.py:73-97`) with a
 ``PopulationRollout`` as the objective: every candidate's episode runs in one launch
 (``mrl_pop_rollout`` for the 64-64 net, ``mrl_pop_rollout_mlp`` for the agent's other
-``hid_sizes``, the reference battery's 10,5 among them).  Observation filter: the reference pushes every observation of every
+``hid_sizes``, the reference battery's 10,5 among them; ``mrl_pop_rollout_wave``, a wave per
+candidate, on Humanoid-v2 -- ``envs.population_rollout`` picks).  Observation filter: the reference pushes every observation of every
 candidate into one shared ``ZFilter`` in serial order (with ``parallel=1`` each worker
 updates a private copy that is never merged).  Here the filter is *frozen* during a
 generation -- all candidates of a generation see the same normalisation -- and the
@@ -122,7 +123,7 @@ def merge_stat_partials(state, stat, obs_dim):
 
 def run_cem_algorithm(env, agent, usercfg=None, callback=None):
     """`cem.py:73-97`: CEM over the agent's flat parameters with whole-episode returns."""
-    from .envs import PopulationRollout
+    from .envs import population_rollout
     cfg = update_default_config(CEM_OPTIONS, usercfg)
     cfg.update(usercfg or {})
     # after the merge: a command line always carries the option's own default (-1.0), and the
@@ -133,8 +134,8 @@ def run_cem_algorithm(env, agent, usercfg=None, callback=None):
     print("cem config", {k: cfg[k] for k in sorted(cfg) if np.ndim(cfg[k]) == 0 or isinstance(cfg[k], (list, str))})
     seed = int(cfg.get("seed", 0) or 0)
     hid = tuple(getattr(getattr(agent.policy, "net", None), "hid_sizes", None) or (64, 64))
-    pop = PopulationRollout(env, cfg["batch_size"], seed=seed, timestep_limit=cfg["timestep_limit"] or None,
-                            hid_sizes=hid)
+    pop = population_rollout(env, cfg["batch_size"], seed=seed, timestep_limit=cfg["timestep_limit"] or None,
+                             hid_sizes=hid)
     if pop.P != agent.get_flat().size:
         raise _lib.MrlError(f"run_cem_algorithm: the agent's {agent.get_flat().size} parameters are not the "
                             f"{pop.P} of the env's tanh MLP with hid_sizes={list(hid)}")

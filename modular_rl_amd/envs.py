@@ -244,10 +244,14 @@ class PopulationRollout:
     shape -- ``(10, 5)`` of the reference's CEM battery, ``()`` for the linear policy -- runs on
     ``mrl_pop_rollout_mlp``, which keeps a block's 64 candidates in LDS for the whole episode:
     up to three hidden layers of 1 .. 64 units whose population tile fits one block's LDS
-    (``mrl_pop_rollout_mlp_fits``); a shape that does not raises ``MrlError`` here.
+    (``mrl_pop_rollout_mlp_fits``); a shape that does not raises ``MrlError`` here, and so
+    does ``Humanoid-v2``, which a wave steps, not a thread: ``WavePopulationRollout`` below is
+    its class and ``population_rollout(env, n, ...)`` picks the class that serves an env.
     """
 
-    def __init__(self, env_id, n, seed=0, timestep_limit=None, env_offset=0, device="cuda", hid_sizes=(64, 64)):
+    DEFAULT_HID = (64, 64)
+
+    def __init__(self, env_id, n, seed=0, timestep_limit=None, env_offset=0, device="cuda", hid_sizes=None):
         env = env_id if isinstance(env_id, DeviceEnv) else DeviceEnv(env_id)
         if int(n) <= 0:
             raise ValueError(f"n must be positive, got {n}")
@@ -258,23 +262,9 @@ class PopulationRollout:
         self.limit = min(limit, env.spec.max_episode_steps)
         self.desc = _lib.RolloutDesc(env.kind, self.N, 1, self.limit, 0, int(env_offset),
                                      int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.COMPUTE_F32, 0)
-        self.hid_sizes = tuple(int(h) for h in hid_sizes)
-        if self.hid_sizes == (64, 64):
-            head = _lib.HEAD_SOFTMAX if env.discrete else _lib.HEAD_GAUSS
-            self.pol = _lib.MlpDesc(env.obs_dim, env.act_dim, head, 64, 2)
-            self.P = int(lib.mrl_mlp_num_params(ctypes.byref(self.pol)))
-        else:
-            self.pol = None
-            self._hid = (ctypes.c_int32 * max(len(self.hid_sizes), 1))(*self.hid_sizes)
-            fits = int(lib.mrl_pop_rollout_mlp_fits(env.kind, self._hid, len(self.hid_sizes)))
-            _lib.check(min(fits, 0), "mrl_pop_rollout_mlp_fits")
-            if fits != 1:
-                raise _lib.MrlError(f"PopulationRollout: hid_sizes={list(self.hid_sizes)} on {env.spec.id} is neither "
-                                    "the 64-64 net nor a net mrl_pop_rollout_mlp takes (every env but Humanoid, at "
-                                    "most 3 hidden layers of 1..64 units, 64 candidates' parameters within one "
-                                    "block's LDS)")
-            self.P = int(lib.mrl_pop_mlp_num_params(env.kind, self._hid, len(self.hid_sizes)))
-            _lib.check(min(self.P, 0), "mrl_pop_mlp_num_params")
+        self.hid_sizes = tuple(int(h) for h in (self.DEFAULT_HID if hid_sizes is None else hid_sizes))
+        self._hid = (ctypes.c_int32 * max(len(self.hid_sizes), 1))(*self.hid_sizes)
+        self._bind(lib)
         N, O = self.N, env.obs_dim
         f64 = dict(dtype=torch.float64, device=self.dev)
         self.env_state = torch.zeros(int(lib.mrl_env_state_doubles(env.kind)) * N, **f64)
@@ -285,6 +275,37 @@ class PopulationRollout:
         self.stat = torch.zeros(N, 1 + 2 * O, **f64)
         self._trace = None
         self._bufs = _lib.RolloutBufs(env_state=_lib.ptr(self.env_state), env_int=_lib.ptr(self.env_int))
+
+    def _bind(self, lib):
+        """The entry point that takes ``hid_sizes`` on this env, and ``P``; ``MrlError`` if none does."""
+        env = self.env
+        if self.hid_sizes == (64, 64) and env.kind != _lib.ENV_HUMANOID:
+            head = _lib.HEAD_SOFTMAX if env.discrete else _lib.HEAD_GAUSS
+            self.pol = _lib.MlpDesc(env.obs_dim, env.act_dim, head, 64, 2)
+            self.P = int(lib.mrl_mlp_num_params(ctypes.byref(self.pol)))
+            return
+        self.pol = None
+        fits = int(lib.mrl_pop_rollout_mlp_fits(env.kind, self._hid, len(self.hid_sizes)))
+        _lib.check(min(fits, 0), "mrl_pop_rollout_mlp_fits")
+        if fits != 1:
+            raise _lib.MrlError(f"PopulationRollout: hid_sizes={list(self.hid_sizes)} on {env.spec.id} is neither "
+                                "the 64-64 net nor a net mrl_pop_rollout_mlp takes (the thread-per-env envs, at "
+                                "most 3 hidden layers of 1..64 units, 64 candidates' parameters within one "
+                                "block's LDS); envs.population_rollout(env, n, ...) picks the class that serves "
+                                "an env, WavePopulationRollout for Humanoid-v2")
+        self._num_params(lib)
+
+    def _num_params(self, lib):
+        self.P = int(lib.mrl_pop_mlp_num_params(self.env.kind, self._hid, len(self.hid_sizes)))
+        _lib.check(min(self.P, 0), "mrl_pop_mlp_num_params")
+
+    def _launch(self, thetas, ld, fs, io):
+        if self.pol is not None:
+            _lib.call("mrl_pop_rollout", ctypes.byref(self.desc), ctypes.byref(self._bufs), ctypes.byref(self.pol),
+                      thetas, ld, fs, ctypes.byref(io), _lib.stream())
+        else:
+            _lib.call("mrl_pop_rollout_mlp", ctypes.byref(self.desc), ctypes.byref(self._bufs), self._hid,
+                      len(self.hid_sizes), thetas, ld, fs, ctypes.byref(io), _lib.stream())
 
     @property
     def episodes_started(self):
@@ -313,12 +334,7 @@ class PopulationRollout:
             tobs, tact, trew = self._trace_bufs(int(trace_steps))
             io.trace_steps, io.trace_obs, io.trace_act, io.trace_rew = int(trace_steps), p(tobs), p(tact), p(trew)
             out.update(trace_obs=tobs, trace_act=tact, trace_rew=trew)
-        if self.pol is not None:
-            _lib.call("mrl_pop_rollout", ctypes.byref(self.desc), ctypes.byref(self._bufs), ctypes.byref(self.pol),
-                      p(thetas), ld, p(fs), ctypes.byref(io), _lib.stream())
-        else:
-            _lib.call("mrl_pop_rollout_mlp", ctypes.byref(self.desc), ctypes.byref(self._bufs), self._hid,
-                      len(self.hid_sizes), p(thetas), ld, p(fs), ctypes.byref(io), _lib.stream())
+        self._launch(p(thetas), ld, p(fs), io)
         return out
 
     def _theta(self, th, shape):
@@ -333,3 +349,41 @@ class PopulationRollout:
     def evaluate(self, theta, filter_state=None, trace_steps=0):
         """The same ``theta`` in all ``n`` envs: a trained policy's return over ``n`` episodes."""
         return self._run(self._theta(theta, (self.P,)), 0, filter_state, trace_steps)
+
+
+class WavePopulationRollout(PopulationRollout):
+    """``PopulationRollout`` for the wave-per-env envs -- ``Humanoid-v2`` -- on
+    ``mrl_pop_rollout_wave``: one wave per candidate keeps its env's state in LDS for the whole
+    episode and reads theta from memory every step.  The interface is ``PopulationRollout``'s
+    (``__call__``, ``evaluate``, ``episodes_started``, ``P``, ``limit``, ``trace_steps``); a
+    ``VecEnv`` of the same seed replays a traced call bit for bit.  ``hid_sizes`` defaults to
+    ``(10, 5)``, the reference's CEM battery: at most three hidden layers of 1 .. 64 units
+    (``mrl_pop_rollout_wave_fits``); any other shape, or a thread-per-env env, raises
+    ``MrlError`` here."""
+
+    DEFAULT_HID = (10, 5)
+
+    def _bind(self, lib):
+        self.pol = None
+        fits = int(lib.mrl_pop_rollout_wave_fits(self.env.kind, self._hid, len(self.hid_sizes)))
+        _lib.check(min(fits, 0), "mrl_pop_rollout_wave_fits")
+        if fits != 1:
+            raise _lib.MrlError(f"WavePopulationRollout: hid_sizes={list(self.hid_sizes)} on {self.env.spec.id} is not "
+                                "a net mrl_pop_rollout_wave takes (Humanoid-v2, at most 3 hidden layers of 1..64 "
+                                "units); envs.population_rollout(env, n, ...) picks the class that serves an env")
+        self._num_params(lib)
+
+    def _launch(self, thetas, ld, fs, io):
+        _lib.call("mrl_pop_rollout_wave", ctypes.byref(self.desc), ctypes.byref(self._bufs), self._hid,
+                  len(self.hid_sizes), thetas, ld, fs, ctypes.byref(io), _lib.stream())
+
+
+def population_rollout(env, n, *, hid_sizes=None, **kw):
+    """The population rollout that serves ``env`` (an id or a ``DeviceEnv``): a
+    ``WavePopulationRollout`` for the wave-per-env envs (Humanoid-v2), a ``PopulationRollout``
+    for the thread-per-env ones.  ``hid_sizes=None`` is the class's default: ``(10, 5)`` for
+    Humanoid, ``(64, 64)`` otherwise.  ``kw``: ``seed``, ``timestep_limit``, ``env_offset``,
+    ``device``."""
+    env = env if isinstance(env, DeviceEnv) else DeviceEnv(env)
+    cls = WavePopulationRollout if env.kind == _lib.ENV_HUMANOID else PopulationRollout
+    return cls(env, n, hid_sizes=hid_sizes, **kw)
