@@ -26,10 +26,6 @@ build/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-# the evaluation units compile their training unit's text (its EV kernel instantiations)
-build/rollout_eval.o build/ubsan/rollout_eval.o: $(CSRC)/rollout.hip
-build/rollout_layered_eval.o build/ubsan/rollout_layered_eval.o: $(CSRC)/rollout_layered.hip
-
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS)
 

@@ -206,7 +206,7 @@ class Collector:
         self.ep_t = torch.zeros(self.N, dtype=torch.int32, device=self.dev)
         self.noise = None  # injected noise rows (parity mode); None: Philox rows drawn per iteration
         self._noise_rows = torch.zeros(int(lib.mrl_rollout_noise_doubles(ctypes.byref(self.desc))), **f64)
-        self.stamps = None  # diagnostic [T, 16] int64 phase stamps (STAMP / PSTAMP in rollout.hip, hm_act_kernel in rollout_layered.hip); None in production
+        self.stamps = None  # diagnostic [T, 16] int64 phase stamps (STAMP / PSTAMP in rollout_kernels.h, hm_act_kernel in rollout_layered_kernels.h); None in production
         net = policy.net
         self.layered = bool(getattr(net, "layered", False))
         # Humanoid steps one env per wave (humanoid.h): its chain wants one wave per SIMD

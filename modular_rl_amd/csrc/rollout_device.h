@@ -1,5 +1,6 @@
-// Device code shared by the rollout units -- rollout.hip (the fused 64-64 path),
-// rollout_layered.hip (the layered path), env_api.hip (the stand-alone env stepper and obs
+// Device code shared by the rollout units -- rollout.hip and rollout_eval.hip (the fused 64-64
+// path, kernel templates in rollout_kernels.h), rollout_layered.hip and rollout_layered_eval.hip
+// (the layered path, rollout_layered_kernels.h), env_api.hip (the stand-alone env stepper and obs
 // filter) and pop_rollout*.hip (the population rollouts): the list of the device envs
 // (MRL_ENV_LIST) with what is generated from it -- EnvC<>, env_info(), env_known() -- the launch
 // arguments RollArgs, env reset / sampling noise / sample-and-step / episode bookkeeping, the
@@ -198,6 +199,22 @@ __device__ inline void chan_merge(double& n, double& M, double& S, double nb, do
   S = S + m2b + delta * (mb - newM) * nb;
   M = newM;
   n = nn;
+}
+
+// the filter's mean and denominator std + 1e-8 of a column with running stat (n, M, S)
+__device__ inline void filter_column(double n, double M, double S, double& mean, double& den) {
+  const double var = n > 1.0 ? S / (n - 1.0) : M * M;  // running_stat.py:27
+  mean = M;
+  den = sqrt(var) + 1e-8;
+}
+
+// column k's running stat (n, M, S) into a filter state of D columns; the obs count is column
+// 0's, the reward count the reward column's
+__device__ inline void store_filter_column(double* fs, int D, int k, double n, double M, double S) {
+  if (k == 0) fs[0] = n;
+  if (k == D - 1) fs[1] = n;
+  fs[2 + k] = M;
+  fs[2 + D + k] = S;
 }
 
 // Sampling noise of env e at step t is Philox (gid, iteration*T + t) on domain 0:

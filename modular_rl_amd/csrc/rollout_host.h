@@ -1,5 +1,6 @@
-// Host-side glue shared by the rollout units -- rollout.hip, rollout_layered.hip, env_api.hip
-// and the population rollouts pop_rollout*.hip: the descriptor checks, the launch arguments,
+// Host-side glue shared by the rollout units -- rollout.hip and rollout_layered.hip with their
+// evaluation units rollout_eval.hip and rollout_layered_eval.hip, env_api.hip and the
+// population rollouts pop_rollout*.hip: the descriptor checks, the launch arguments,
 // the dispatch of an env id (over rollout_device.h's MRL_ENV_LIST) or a flag onto a kernel
 // template, and the launch of the Humanoid wave-per-env kernels.  The error state (fail /
 // hip_check, mrl_common.h) is mlp_kernels.hip's.
@@ -148,9 +149,9 @@ inline size_t hm_lds_bytes(int wpb, int n_envs) { return wpb == 1 ? hm_lds_pad(n
 void launch_hm_env_reset(const RollArgs& a, const mrl_env_io& io, hipStream_t s);
 void launch_hm_env_step(const RollArgs& a, const mrl_env_io& io, int auto_reset, hipStream_t s);
 
-// The evaluation instantiations (MRL_ROLLOUT_EVAL) of the rollout kernels, compiled in units of
-// their own -- rollout_eval.hip and rollout_layered_eval.hip -- for the entry points of
-// rollout.hip and rollout_layered.hip, which have checked the arguments.
+// The evaluation instantiations (MRL_ROLLOUT_EVAL) of the kernel templates of rollout_kernels.h
+// and rollout_layered_kernels.h, defined in rollout_eval.hip and rollout_layered_eval.hip for the
+// entry points of rollout.hip and rollout_layered.hip, which have checked the arguments.
 void launch_rollout_reset_eval(const RollArgs& a, hipStream_t s);
 void launch_rollout_step_eval(const RollArgs& a, bool bf, const float* logstd, const float* rimage, int t,
                               hipStream_t s);

@@ -5,8 +5,8 @@ rewfilt) for E envs in lock-step, with the batched-filter rule of SURVEY Appendi
 A.1 (all E observations of a step merged into the running stat -- as per-block
 Welford partials in block order -- then normalised).  For E = 1 this is exactly
 the reference's sequence of RunningStat.push calls.  Mirrors the rollout units of
-``modular_rl_amd/csrc`` (``rollout.hip`` the fused path, ``rollout_layered.hip`` the
-layered one, ``rollout_device.h`` what they share) step for step so the GPU collector
+``modular_rl_amd/csrc`` (``rollout_kernels.h`` the fused path, ``rollout_layered_kernels.h``
+the layered one, ``rollout_device.h`` what they share) step for step so the GPU collector
 can be checked row by row; the policy forward here is float64 on the stored float32
 observations.
 """

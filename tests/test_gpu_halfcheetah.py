@@ -1,7 +1,7 @@
 """HalfCheetah-v2 on the device, through every layer that steps an env: VecEnv against the numpy
 twin (tests/halfcheetah_np.py), written states in the floor, past every hinge stop and sliding
 on a foot, the fused rollout (step launches and the persistent launch; 18 filter columns, so the
-second column pass of rollout.hip) and the layered rollout against oracle.rollout_np.collect on
+second column pass of rollout_kernels.h) and the layered rollout against oracle.rollout_np.collect on
 the twin, the population rollout (both kernels) replayed through a VecEnv, and run_pg.py /
 run_cem_algorithm end to end.  Sizes and tolerances are tests/test_gpu_planar_chains.py's."""
 import json

@@ -1,6 +1,6 @@
 """Diagnostic: per-phase s_memrealtime stamps of one rollout_step launch (block 0).
 
-Phases (STAMP ids of rollout_step_kernel, rollout.hip, and of forward16 in time order):
+Phases (STAMP ids of rollout_step_kernel, rollout_kernels.h, and of forward16, rollout_forward.h, in time order):
 0 start | 1 loads issued | 2 filter merge |
 3 filtered obs | 9 forward layer 0 | 10 layer 1 | 4 head | 5 sample+env step |
 6 finish+obs+sync | 7 publish partial.
