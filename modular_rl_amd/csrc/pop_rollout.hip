@@ -18,20 +18,14 @@
 // their stores masked until the wave's last episode ends; the loop is bounded by the step
 // counter.  No block waits on another and nothing is accumulated across lanes: the results do
 // not depend on scheduling.
-#include "rollout_host.h"
+// The argument block is pop_rollout_device.h's, the argument checks pop_rollout_host.h's.  The
+// episode protocol (frozen filter, filter / clip / cast, Welford, traces, action and step,
+// result stores) is written out here as in the other lane kernel: DESIGN 5g has the folds tried.
+#include "pop_rollout_host.h"
 
 namespace mrl {
 
-constexpr int POP_W = 64;          // candidates per block (one wave)
 constexpr int POP_LD = POP_W + 1;  // LDS tile stride in floats
-
-struct PopArgs {
-  const float* thetas;
-  int64_t ld;
-  const double* fstate;
-  mrl_pop_io io;
-  int limit;  // steps an episode may take: min(timestep_limit or MAX_STEPS, MAX_STEPS)
-};
 
 template <int ENV>
 __global__ __launch_bounds__(POP_W) void pop_rollout_kernel(RollArgs a, PopArgs p) {
@@ -53,7 +47,9 @@ __global__ __launch_bounds__(POP_W) void pop_rollout_kernel(RollArgs a, PopArgs 
   const float* __restrict__ th0 = p.thetas + (int64_t)e0 * p.ld;
 
   // frozen filter: mrl_obfilter_update_apply(update = 0); below two observations (or no state)
-  // mean 0 / denominator 1, which leaves the observation bit for bit
+  // mean 0 / denominator 1, which leaves the observation bit for bit.  Written out, like the
+  // rest of the episode below: load-bearing, every fold into a shared function
+  // moved this kernel's register allocation for some env
   if (lane < O) {
     double M = 0.0, den = 1.0;
     if (p.fstate != nullptr && p.fstate[0] >= 2.0) {
@@ -229,23 +225,7 @@ using namespace mrl;
 extern "C" int mrl_pop_rollout(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, const mrl_mlp_desc* pol,
                                const float* thetas, int64_t ld_theta, const double* filter_state,
                                const mrl_pop_io* io, void* stream) {
-  const char* what = nullptr;
-  if (!d) what = "null desc";
-  else if (!b) what = "null bufs";
-  else if (!pol) what = "null policy desc";
-  else if (!thetas) what = "null thetas";
-  else if (!io) what = "null io";
-  else if (!env_known(d->env_id)) what = "desc.env_id: unknown env";
-  else if (d->n_envs <= 0) what = "desc.n_envs <= 0";
-  else if (!b->env_state) what = "null bufs.env_state";
-  else if (!b->env_int) what = "null bufs.env_int";
-  else if (!io->ret || !io->len || !io->flags || !io->stat) what = "null io.ret / len / flags / stat";
-  else if (io->trace_steps < 0) what = "io.trace_steps < 0";
-  else {
-    const bool any = io->trace_obs || io->trace_act || io->trace_rew || io->trace_steps > 0;
-    const bool all = io->trace_obs && io->trace_act && io->trace_rew && io->trace_steps > 0;
-    if (any && !all) what = "the trace is only partly set (trace_steps, trace_obs, trace_act, trace_rew)";
-  }
+  const char* what = pop_check_args(d, b, pol ? nullptr : "null policy desc", thetas, io);
   if (what) return fail(E_ARG, std::string("mrl_pop_rollout: ") + what);
   if (d->env_id == MRL_ENV_HUMANOID)
     return fail(E_UNSUPPORTED, "mrl_pop_rollout: Humanoid is not supported (the thread-per-env envs only)");
@@ -259,11 +239,7 @@ extern "C" int mrl_pop_rollout(const mrl_rollout_desc* d, const mrl_rollout_bufs
   if (ld_theta != 0 && ld_theta < P) return fail(E_ARG, "mrl_pop_rollout: ld_theta is neither 0 nor >= the parameter count");
   RollArgs a = make_args(d, b);
   PopArgs p;
-  p.thetas = thetas;
-  p.ld = ld_theta;
-  p.fstate = filter_state;
-  p.io = *io;
-  p.limit = d->timestep_limit > 0 && d->timestep_limit < ei.max_steps ? d->timestep_limit : ei.max_steps;
+  pop_fill(p, d, thetas, ld_theta, filter_state, io);
   const dim3 grid((d->n_envs + POP_W - 1) / POP_W);
   MRL_DISPATCH_THREAD_ENV(d->env_id, pop_rollout_kernel, grid, dim3(POP_W), 0, (hipStream_t)stream, a, p);
   return hip_check(hipGetLastError(), "mrl_pop_rollout");

@@ -35,25 +35,16 @@
 // every call, and ld_theta = 0 (one shared theta) the bits of N copies.
 // f32 values go to LDS through an identity DPP move (rows_epilogue.h st_head's idiom): an LDS
 // op must not read a packed-f32 VALU result within 8 wait states.
-#include "rollout_host.h"
+//
+// The frozen filter's column, filter / clip / cast and the Welford update are
+// pop_rollout_device.h's, as in the lane kernels; the argument checks pop_rollout_host.h's.
+#include "pop_rollout_host.h"
 
 namespace mrl {
 
-constexpr int HP_MAX_HID = 3;     // hidden layers
-constexpr int HP_MAX_WIDTH = 64;  // units per hidden layer: one lane per unit
+constexpr int HP_MAX_WIDTH = POP_MAX_WIDTH;  // units per hidden layer: one lane per unit
 constexpr int HP_JB = 8;          // layer-0 outputs accumulated per pass over a lane's inputs
 constexpr int HP_CPL = (HM_OBS + 63) / 64;  // observation columns per lane
-constexpr size_t HP_LDS_LIMIT = 160 * 1024;  // one block's LDS on gfx950
-
-struct HmPopArgs {
-  const float* thetas;
-  int64_t ld;
-  const double* fstate;
-  mrl_pop_io io;
-  int limit;  // steps an episode may take: min(timestep_limit or MAX_STEPS, MAX_STEPS)
-  int n_hid;
-  int dims[HP_MAX_HID + 2];  // obs, hid_sizes..., act
-};
 
 // a wave's own LDS beside its hm::Wave: the raw observation, the filtered one, two activation rows
 struct HmPopWave {
@@ -68,7 +59,7 @@ inline size_t hm_pop_lds_bytes(int wpb, int) {
   return hm_lds_state(wpb, 0) + (size_t)2 * HM_OBS * sizeof(double) + (size_t)wpb * sizeof(HmPopWave);
 }
 static_assert(sizeof(hm::Shared) + 4 * sizeof(hm::Wave) + 2 * HM_OBS * sizeof(double) + 4 * sizeof(HmPopWave) <=
-                  HP_LDS_LIMIT,
+                  LDS_PER_BLOCK,
               "four candidates per block exceed the LDS");
 
 __device__ __forceinline__ void hp_st_lds(float* p, float v) { *p = dpp_f<0xE4>(v); }
@@ -76,14 +67,14 @@ __device__ __forceinline__ void hp_st_lds(float* p, float v) { *p = dpp_f<0xE4>(
 // the head row of theta `th` on the filtered observation X.x: lane j < 17 returns z_j
 __device__ inline float hp_policy(const HmPopArgs& p, const float* __restrict__ th, HmPopWave& X, int lane) {
   constexpr int O = HM_OBS;
-  const int n_hid = p.n_hid;
+  const int n_hid = p.sh.n_hid;
   float xv[HP_CPL];
 #pragma unroll
   for (int i = 0; i < HP_CPL; ++i) xv[i] = lane + 64 * i < O ? X.x[lane + 64 * i] : 0.f;
   float val = 0.f;
   int off = 0;
   for (int l = 0; l <= n_hid; ++l) {
-    const int din = p.dims[l], dout = p.dims[l + 1];
+    const int din = p.sh.dims[l], dout = p.sh.dims[l + 1];
     const float* __restrict__ Wl = th + off;  // W[k][j] at Wl[k dout + j]
     const float* __restrict__ bl = Wl + din * dout;
     const float* hin = X.h[(l + 1) & 1];
@@ -142,16 +133,10 @@ __global__ __launch_bounds__(64 * WPB) void hm_pop_rollout_kernel(RollArgs a, Hm
   const int wave = WPB == 1 ? 0 : __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   HmPopWave& X = reinterpret_cast<HmPopWave*>(fden + O)[wave];
 
-  // frozen filter: mrl_obfilter_update_apply(update = 0); below two observations (or no state)
-  // mean 0 / denominator 1, which leaves the observation bit for bit.  One copy per block,
-  // written by all its waves before the tables' barrier.
+  // the frozen filter: one copy per block, written by all its waves before the tables' barrier
   for (int k = threadIdx.x; k < O; k += 64 * WPB) {
-    double M = 0.0, den = 1.0;
-    if (p.fstate != nullptr && p.fstate[0] >= 2.0) {
-      const double n = p.fstate[0];
-      M = p.fstate[2 + k];
-      den = sqrt(p.fstate[2 + D + k] / (n - 1.0)) + 1e-8;
-    }
+    double M, den;
+    pop_frozen_filter(p.fstate, D, k, M, den);
     fmean[k] = M;
     fden[k] = den;
   }
@@ -196,12 +181,8 @@ __global__ __launch_bounds__(64 * WPB) void hm_pop_rollout_kernel(RollArgs a, Hm
         if (k < O) {
           const double o = X.od[k];
           if (tr) orow[k] = o;
-          const double dlt = o - wmean[i];
-          wmean[i] += dlt / wn;
-          wm2[i] += dlt * (o - wmean[i]);
-          double v = o - fmean[k];
-          v = v / fden[k];
-          X.x[k] = (float)(v < -5.0 ? -5.0 : (v > 5.0 ? 5.0 : v));
+          welford_add(o, wn, wmean[i], wm2[i]);
+          X.x[k] = pop_filtered(o, fmean[k], fden[k]);
         }
       }
       WAVE_SYNC();
@@ -239,71 +220,33 @@ __global__ __launch_bounds__(64 * WPB) void hm_pop_rollout_kernel(RollArgs a, Hm
   hm::save_kcache(W, a.b.env_state + (int64_t)HM_NS * N + (int64_t)e * HM_KCACHE, lane);
 }
 
-// 1: a net this kernel takes; 0: another env or shape; E_ARG (`what` names the check)
-static int hp_fits(int32_t env_id, const int32_t* hid_sizes, int32_t n_hid, const char*& what) {
-  if (!env_known(env_id)) return what = "desc.env_id: unknown env", E_ARG;
-  if (n_hid < 0) return what = "n_hid < 0", E_ARG;
-  if (n_hid > 0 && !hid_sizes) return what = "null hid_sizes", E_ARG;
-  if (env_id != MRL_ENV_HUMANOID) return what = "the wave-per-env envs only (Humanoid)", 0;
-  if (n_hid > HP_MAX_HID) return what = "more than 3 hidden layers", 0;
-  for (int l = 0; l < n_hid; ++l)
-    if (hid_sizes[l] < 1 || hid_sizes[l] > HP_MAX_WIDTH) return what = "a hidden width outside [1, 64]", 0;
-  return 1;
-}
-
 }  // namespace mrl
 
 using namespace mrl;
 
+// 1: a net this kernel takes; 0: another env or shape; E_ARG
 extern "C" int32_t mrl_pop_rollout_wave_fits(int32_t env_id, const int32_t* hid_sizes, int32_t n_hid) {
+  PopSmallShape sh;
   const char* what = nullptr;
-  const int rc = hp_fits(env_id, hid_sizes, n_hid, what);
-  if (rc < 0) return fail(rc, std::string("mrl_pop_rollout_wave_fits: ") + what);
-  return rc;
+  const int rc = pop_net_shape(env_id, hid_sizes, n_hid, true, sh, what);
+  if (rc == E_ARG) return fail(E_ARG, std::string("mrl_pop_rollout_wave_fits: ") + what);
+  return rc == OK ? 1 : 0;
 }
 
 extern "C" int mrl_pop_rollout_wave(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, const int32_t* hid_sizes,
                                     int32_t n_hid, const float* thetas, int64_t ld_theta, const double* filter_state,
                                     const mrl_pop_io* io, void* stream) {
-  const char* what = nullptr;
-  if (!d) what = "null desc";
-  else if (!b) what = "null bufs";
-  else if (n_hid < 0) what = "n_hid < 0";
-  else if (n_hid > 0 && !hid_sizes) what = "null hid_sizes";
-  else if (!thetas) what = "null thetas";
-  else if (!io) what = "null io";
-  else if (!env_known(d->env_id)) what = "desc.env_id: unknown env";
-  else if (d->n_envs <= 0) what = "desc.n_envs <= 0";
-  else if (!b->env_state) what = "null bufs.env_state";
-  else if (!b->env_int) what = "null bufs.env_int";
-  else if (!io->ret || !io->len || !io->flags || !io->stat) what = "null io.ret / len / flags / stat";
-  else if (io->trace_steps < 0) what = "io.trace_steps < 0";
-  else {
-    const bool any = io->trace_obs || io->trace_act || io->trace_rew || io->trace_steps > 0;
-    const bool all = io->trace_obs && io->trace_act && io->trace_rew && io->trace_steps > 0;
-    if (any && !all) what = "the trace is only partly set (trace_steps, trace_obs, trace_act, trace_rew)";
-  }
+  const char* what = pop_check_args(d, b, pop_check_hid(hid_sizes, n_hid), thetas, io);
   if (what) return fail(E_ARG, std::string("mrl_pop_rollout_wave: ") + what);
-  const int fits = hp_fits(d->env_id, hid_sizes, n_hid, what);
-  if (fits < 0) return fail(fits, std::string("mrl_pop_rollout_wave: ") + what);
-  if (fits != 1) return fail(E_UNSUPPORTED, std::string("mrl_pop_rollout_wave: ") + what);
-  const EnvInfo ei = env_info(d->env_id);
-  HmPopArgs p;
-  p.n_hid = n_hid;
-  p.dims[0] = ei.obs;
-  for (int l = 0; l < n_hid; ++l) p.dims[1 + l] = hid_sizes[l];
-  p.dims[n_hid + 1] = ei.act;
-  for (int l = n_hid + 2; l < HP_MAX_HID + 2; ++l) p.dims[l] = 0;
-  int64_t P = ei.act;  // logstd
-  for (int l = 0; l <= n_hid; ++l) P += (int64_t)p.dims[l] * p.dims[l + 1] + p.dims[l + 1];
-  if (ld_theta != 0 && ld_theta < P)
+  PopSmallShape net;
+  const int rc = pop_net_shape(d->env_id, hid_sizes, n_hid, true, net, what);
+  if (rc) return fail(rc, std::string("mrl_pop_rollout_wave: ") + what);
+  if (ld_theta != 0 && ld_theta < pop_num_params(env_info(d->env_id), net.PU))
     return fail(E_ARG, "mrl_pop_rollout_wave: ld_theta is neither 0 nor >= the parameter count");
   RollArgs a = make_args(d, b);
-  p.thetas = thetas;
-  p.ld = ld_theta;
-  p.fstate = filter_state;
-  p.io = *io;
-  p.limit = d->timestep_limit > 0 && d->timestep_limit < ei.max_steps ? d->timestep_limit : ei.max_steps;
+  HmPopArgs p;
+  p.sh = net.sh;
+  pop_fill(p, d, thetas, ld_theta, filter_state, io);
   MRL_LAUNCH_HM(hm_pop_rollout_kernel, hm_pop_lds_bytes, d->n_envs, (hipStream_t)stream, a, p);
   return hip_check(hipGetLastError(), "mrl_pop_rollout_wave");
 }

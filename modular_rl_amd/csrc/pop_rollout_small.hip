@@ -16,39 +16,24 @@
 // for k ascending, acc + b_j, tanhf on hidden layers; the same fp64 filter expressions and cast;
 // the same physics (EnvC<>, reset_env).  A 10-5 net zero-padded to 64-64 gives the same bits in
 // both kernels.
-#include "rollout_host.h"
+//
+// The argument block is pop_rollout_device.h's, the argument checks pop_rollout_host.h's.  The
+// episode protocol (frozen filter, filter / clip / cast, Welford, traces, action and step,
+// result stores) is written out here as in the other lane kernel: DESIGN 5g has the folds tried.
+#include "pop_rollout_host.h"
 
 namespace mrl {
 
-constexpr int PS_W = 64;              // candidates per block (one wave)
-constexpr int PS_LD = PS_W + 1;       // LDS tile stride in floats
-constexpr int PS_MAX_HID = 3;         // hidden layers
-constexpr int PS_MAX_WIDTH = 64;      // units per hidden layer
-constexpr int PS_JB = 4;              // outputs accumulated per pass over a layer's inputs
-constexpr size_t PS_LDS_LIMIT = 160 * 1024;  // one block's LDS on gfx950
-
-struct PopSmallShape {
-  int n_hid;
-  int dims[PS_MAX_HID + 2];  // obs, hid_sizes..., act
-  int PU;                    // floats of theta the forward reads (all but logstd)
-  int maxw;                  // widest layer, input and head included
-};
-
-struct PopSmallArgs {
-  const float* thetas;
-  int64_t ld;
-  const double* fstate;
-  mrl_pop_io io;
-  int limit;  // steps an episode may take: min(timestep_limit or MAX_STEPS, MAX_STEPS)
-  PopSmallShape sh;
-};
+constexpr int PS_W = POP_W;      // candidates per block (one wave)
+constexpr int PS_LD = PS_W + 1;  // LDS tile stride in floats
+constexpr int PS_JB = 4;         // outputs accumulated per pass over a layer's inputs
 
 // dynamic LDS of a block: the frozen filter (mean, denominator), the theta tile, two
 // activation buffers.  The launch and mrl_pop_rollout_mlp_fits both go through here.
 inline size_t ps_filter_bytes(int obs) { return (size_t)2 * obs * sizeof(double); }
-inline size_t ps_tile_bytes(const PopSmallShape& sh) { return (size_t)sh.PU * PS_LD * sizeof(float); }
-inline size_t ps_lds_bytes(const PopSmallShape& sh) {
-  return ps_filter_bytes(sh.dims[0]) + ps_tile_bytes(sh) + (size_t)2 * sh.maxw * PS_W * sizeof(float);
+inline size_t ps_tile_bytes(const PopSmallShape& net) { return (size_t)net.PU * PS_LD * sizeof(float); }
+inline size_t ps_lds_bytes(const PopSmallShape& net) {
+  return ps_filter_bytes(net.sh.dims[0]) + ps_tile_bytes(net) + (size_t)2 * net.maxw * PS_W * sizeof(float);
 }
 
 template <int ENV>
@@ -59,9 +44,9 @@ __global__ __launch_bounds__(PS_W) void pop_rollout_small_kernel(RollArgs a, Pop
   double* fmean = ps_dyn;
   double* fden = ps_dyn + O;
   float* tile = reinterpret_cast<float*>(ps_dyn + 2 * O);
-  const int PU = p.sh.PU, n_hid = p.sh.n_hid;
+  const int PU = p.net.PU, n_hid = p.net.sh.n_hid;
   float* buf0 = tile + (size_t)PU * PS_LD;
-  float* buf1 = buf0 + p.sh.maxw * PS_W;
+  float* buf1 = buf0 + p.net.maxw * PS_W;
   const int N = a.d.n_envs;
   const int lane = threadIdx.x;
   const int e0 = blockIdx.x * PS_W;
@@ -70,7 +55,9 @@ __global__ __launch_bounds__(PS_W) void pop_rollout_small_kernel(RollArgs a, Pop
   const float* __restrict__ th0 = p.thetas + (int64_t)e0 * p.ld;
 
   // frozen filter: mrl_obfilter_update_apply(update = 0); below two observations (or no state)
-  // mean 0 / denominator 1, which leaves the observation bit for bit
+  // mean 0 / denominator 1, which leaves the observation bit for bit.  Written out, like the
+  // rest of the episode below: load-bearing, every fold into a shared function
+  // moved this kernel's register allocation for some env
   if (lane < O) {
     double M = 0.0, den = 1.0;
     if (p.fstate != nullptr && p.fstate[0] >= 2.0) {
@@ -142,7 +129,7 @@ __global__ __launch_bounds__(PS_W) void pop_rollout_small_kernel(RollArgs a, Pop
     float* xout = buf1 + lane;
     int off = 0;
     for (int l = 0; l <= n_hid; ++l) {
-      const int din = p.sh.dims[l], dout = p.sh.dims[l + 1];
+      const int din = p.net.sh.dims[l], dout = p.net.sh.dims[l + 1];
       const float* Wl = tl + off * PS_LD;            // W[k][j] at Wl[(k dout + j) PS_LD]
       const float* bl = Wl + din * dout * PS_LD;
       for (int j0 = 0; j0 < dout; j0 += PS_JB) {
@@ -220,97 +207,44 @@ __global__ __launch_bounds__(PS_W) void pop_rollout_small_kernel(RollArgs a, Pop
   }
 }
 
-// the net's shape from the caller's arguments.  E_ARG: an unknown env, n_hid < 0, null
-// hid_sizes with n_hid > 0; E_UNSUPPORTED: Humanoid, more than three hidden layers, a width
-// outside [1, 64].  `what` names the failed check.
-static int ps_shape(int32_t env_id, const int32_t* hid_sizes, int32_t n_hid, PopSmallShape& sh, const char*& what) {
-  if (!env_known(env_id)) return what = "desc.env_id: unknown env", E_ARG;
-  if (n_hid < 0) return what = "n_hid < 0", E_ARG;
-  if (n_hid > 0 && !hid_sizes) return what = "null hid_sizes", E_ARG;
-  if (env_id == MRL_ENV_HUMANOID) return what = "Humanoid is not supported (the thread-per-env envs only)", E_UNSUPPORTED;
-  if (n_hid > PS_MAX_HID) return what = "more than 3 hidden layers", E_UNSUPPORTED;
-  for (int l = 0; l < n_hid; ++l)
-    if (hid_sizes[l] < 1 || hid_sizes[l] > PS_MAX_WIDTH) return what = "a hidden width outside [1, 64]", E_UNSUPPORTED;
-  const EnvInfo ei = env_info(env_id);
-  sh.n_hid = n_hid;
-  sh.dims[0] = ei.obs;
-  for (int l = 0; l < n_hid; ++l) sh.dims[1 + l] = hid_sizes[l];
-  sh.dims[n_hid + 1] = ei.act;
-  for (int l = n_hid + 2; l < PS_MAX_HID + 2; ++l) sh.dims[l] = 0;
-  sh.PU = 0;
-  sh.maxw = 0;
-  for (int l = 0; l <= n_hid; ++l) sh.PU += sh.dims[l] * sh.dims[l + 1] + sh.dims[l + 1];
-  for (int l = 0; l <= n_hid + 1; ++l) sh.maxw = sh.dims[l] > sh.maxw ? sh.dims[l] : sh.maxw;
-  return OK;
-}
-
 }  // namespace mrl
 
 using namespace mrl;
 
 extern "C" int64_t mrl_pop_mlp_num_params(int32_t env_id, const int32_t* hid_sizes, int32_t n_hid) {
   if (!env_known(env_id)) return fail(E_ARG, "mrl_pop_mlp_num_params: unknown env");
-  if (n_hid < 0) return fail(E_ARG, "mrl_pop_mlp_num_params: n_hid < 0");
-  if (n_hid > 0 && !hid_sizes) return fail(E_ARG, "mrl_pop_mlp_num_params: null hid_sizes");
-  const EnvInfo ei = env_info(env_id);
-  int64_t P = 0, din = ei.obs;
-  for (int l = 0; l < n_hid; ++l) {
+  if (const char* what = pop_check_hid(hid_sizes, n_hid)) return fail(E_ARG, std::string("mrl_pop_mlp_num_params: ") + what);
+  for (int l = 0; l < n_hid; ++l)  // a count, not a launch: any number of layers, any width from 1 up
     if (hid_sizes[l] < 1) return fail(E_ARG, "mrl_pop_mlp_num_params: a hidden width < 1");
-    P += din * hid_sizes[l] + hid_sizes[l];
-    din = hid_sizes[l];
-  }
-  P += din * ei.act + ei.act;
-  return P + (ei.discrete ? 0 : ei.act);
+  const EnvInfo ei = env_info(env_id);
+  return pop_num_params(ei, pop_forward_floats(ei, hid_sizes, n_hid));
 }
 
 extern "C" int32_t mrl_pop_rollout_mlp_fits(int32_t env_id, const int32_t* hid_sizes, int32_t n_hid) {
   PopSmallShape sh;
   const char* what = nullptr;
-  const int rc = ps_shape(env_id, hid_sizes, n_hid, sh, what);
+  const int rc = pop_net_shape(env_id, hid_sizes, n_hid, false, sh, what);
   if (rc == E_ARG) return fail(E_ARG, std::string("mrl_pop_rollout_mlp_fits: ") + what);
   if (rc) return 0;
-  return ps_lds_bytes(sh) <= PS_LDS_LIMIT ? 1 : 0;
+  return ps_lds_bytes(sh) <= LDS_PER_BLOCK ? 1 : 0;
 }
 
 extern "C" int mrl_pop_rollout_mlp(const mrl_rollout_desc* d, const mrl_rollout_bufs* b, const int32_t* hid_sizes,
                                    int32_t n_hid, const float* thetas, int64_t ld_theta, const double* filter_state,
                                    const mrl_pop_io* io, void* stream) {
-  const char* what = nullptr;
-  if (!d) what = "null desc";
-  else if (!b) what = "null bufs";
-  else if (n_hid < 0) what = "n_hid < 0";
-  else if (n_hid > 0 && !hid_sizes) what = "null hid_sizes";
-  else if (!thetas) what = "null thetas";
-  else if (!io) what = "null io";
-  else if (!env_known(d->env_id)) what = "desc.env_id: unknown env";
-  else if (d->n_envs <= 0) what = "desc.n_envs <= 0";
-  else if (!b->env_state) what = "null bufs.env_state";
-  else if (!b->env_int) what = "null bufs.env_int";
-  else if (!io->ret || !io->len || !io->flags || !io->stat) what = "null io.ret / len / flags / stat";
-  else if (io->trace_steps < 0) what = "io.trace_steps < 0";
-  else {
-    const bool any = io->trace_obs || io->trace_act || io->trace_rew || io->trace_steps > 0;
-    const bool all = io->trace_obs && io->trace_act && io->trace_rew && io->trace_steps > 0;
-    if (any && !all) what = "the trace is only partly set (trace_steps, trace_obs, trace_act, trace_rew)";
-  }
+  const char* what = pop_check_args(d, b, pop_check_hid(hid_sizes, n_hid), thetas, io);
   if (what) return fail(E_ARG, std::string("mrl_pop_rollout_mlp: ") + what);
   PopSmallArgs p;
-  const int rc = ps_shape(d->env_id, hid_sizes, n_hid, p.sh, what);
+  const int rc = pop_net_shape(d->env_id, hid_sizes, n_hid, false, p.net, what);
   if (rc) return fail(rc, std::string("mrl_pop_rollout_mlp: ") + what);
-  const size_t lds = ps_lds_bytes(p.sh);
-  if (lds > PS_LDS_LIMIT)
+  const size_t lds = ps_lds_bytes(p.net);
+  if (lds > LDS_PER_BLOCK)
     return fail(E_UNSUPPORTED, "mrl_pop_rollout_mlp: 64 candidates of this net need " + std::to_string(lds) +
-                                   " bytes of LDS, a block has " + std::to_string(PS_LDS_LIMIT));
-  const EnvInfo ei = env_info(d->env_id);
-  const int64_t P = p.sh.PU + (ei.discrete ? 0 : ei.act);
-  if (ld_theta != 0 && ld_theta < P)
+                                   " bytes of LDS, a block has " + std::to_string(LDS_PER_BLOCK));
+  if (ld_theta != 0 && ld_theta < pop_num_params(env_info(d->env_id), p.net.PU))
     return fail(E_ARG, "mrl_pop_rollout_mlp: ld_theta is neither 0 nor >= the parameter count");
   RollArgs a = make_args(d, b);
-  p.thetas = thetas;
-  p.ld = ld_theta;
-  p.fstate = filter_state;
-  p.io = *io;
-  p.limit = d->timestep_limit > 0 && d->timestep_limit < ei.max_steps ? d->timestep_limit : ei.max_steps;
+  pop_fill(p, d, thetas, ld_theta, filter_state, io);
   const dim3 grid((d->n_envs + PS_W - 1) / PS_W);
   MRL_DISPATCH_THREAD_ENV(d->env_id, pop_rollout_small_kernel, grid, dim3(PS_W), lds, (hipStream_t)stream, a, p);
   return hip_check(hipGetLastError(), "mrl_pop_rollout_mlp");

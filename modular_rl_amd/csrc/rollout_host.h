@@ -1,6 +1,7 @@
 // Host-side glue shared by the rollout units -- rollout.hip and rollout_layered.hip with their
 // evaluation units rollout_eval.hip and rollout_layered_eval.hip, env_api.hip and the
-// population rollouts pop_rollout*.hip: the descriptor checks, the launch arguments,
+// population rollouts pop_rollout*.hip (whose own checks and shapes are pop_rollout_host.h's,
+// over pop_rollout_device.h): the descriptor checks, the launch arguments,
 // the dispatch of an env id (over rollout_device.h's MRL_ENV_LIST) or a flag onto a kernel
 // template, and the launch of the Humanoid wave-per-env kernels.  The error state (fail /
 // hip_check, mrl_common.h) is mlp_kernels.hip's.
@@ -105,6 +106,9 @@ inline void dispatch_bool(bool b, F&& f) {
   else f(std::false_type{});
 }
 
+// one block's LDS on gfx950 (a CU's whole 160 KB)
+constexpr size_t LDS_PER_BLOCK = 160 * 1024;
+
 // ------------------------------------------------------------------ Humanoid launch
 // Dynamic LDS padding for the wave-per-env Humanoid step: while the envs fit one wave
 // per SIMD, at most 4 blocks (waves) may share a CU, so the dispatcher cannot stack two
@@ -119,7 +123,7 @@ inline size_t hm_lds_pad(int n_envs) {
       ncu = -1;
   }
   if (ncu <= 0 || n_envs > 4 * ncu) return 0;
-  constexpr size_t LDS_CU = 160 * 1024, used = sizeof(hm::Wave) + sizeof(hm::Shared), want = LDS_CU / 5 + 1024;
+  constexpr size_t used = sizeof(hm::Wave) + sizeof(hm::Shared), want = LDS_PER_BLOCK / 5 + 1024;
   return used < want ? want - used : 0;
 }
 // MRL_HM_WPB (per launch): four envs per block (hm_block, the default) or 1

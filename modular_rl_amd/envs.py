@@ -276,36 +276,36 @@ class PopulationRollout:
         self._trace = None
         self._bufs = _lib.RolloutBufs(env_state=_lib.ptr(self.env_state), env_int=_lib.ptr(self.env_int))
 
+    # the entry point that takes hid_sizes, its predicate, and what a shape it turns away is told
+    # (and whether hid_sizes (64, 64) goes to mrl_pop_rollout, the kernel of that one shape)
+    ENTRY, FITS, HAS_64_64 = "mrl_pop_rollout_mlp", "mrl_pop_rollout_mlp_fits", True
+    REFUSAL = ("PopulationRollout: hid_sizes={hid} on {env} is neither "
+               "the 64-64 net nor a net mrl_pop_rollout_mlp takes (the thread-per-env envs, at "
+               "most 3 hidden layers of 1..64 units, 64 candidates' parameters within one "
+               "block's LDS); envs.population_rollout(env, n, ...) picks the class that serves "
+               "an env, WavePopulationRollout for Humanoid-v2")
+
     def _bind(self, lib):
         """The entry point that takes ``hid_sizes`` on this env, and ``P``; ``MrlError`` if none does."""
         env = self.env
-        if self.hid_sizes == (64, 64) and env.kind != _lib.ENV_HUMANOID:
+        if self.HAS_64_64 and self.hid_sizes == (64, 64) and env.kind != _lib.ENV_HUMANOID:
             head = _lib.HEAD_SOFTMAX if env.discrete else _lib.HEAD_GAUSS
             self.pol = _lib.MlpDesc(env.obs_dim, env.act_dim, head, 64, 2)
             self.P = int(lib.mrl_mlp_num_params(ctypes.byref(self.pol)))
             return
         self.pol = None
-        fits = int(lib.mrl_pop_rollout_mlp_fits(env.kind, self._hid, len(self.hid_sizes)))
-        _lib.check(min(fits, 0), "mrl_pop_rollout_mlp_fits")
+        fits = int(getattr(lib, self.FITS)(env.kind, self._hid, len(self.hid_sizes)))
+        _lib.check(min(fits, 0), self.FITS)
         if fits != 1:
-            raise _lib.MrlError(f"PopulationRollout: hid_sizes={list(self.hid_sizes)} on {env.spec.id} is neither "
-                                "the 64-64 net nor a net mrl_pop_rollout_mlp takes (the thread-per-env envs, at "
-                                "most 3 hidden layers of 1..64 units, 64 candidates' parameters within one "
-                                "block's LDS); envs.population_rollout(env, n, ...) picks the class that serves "
-                                "an env, WavePopulationRollout for Humanoid-v2")
-        self._num_params(lib)
-
-    def _num_params(self, lib):
-        self.P = int(lib.mrl_pop_mlp_num_params(self.env.kind, self._hid, len(self.hid_sizes)))
+            raise _lib.MrlError(self.REFUSAL.format(hid=list(self.hid_sizes), env=env.spec.id))
+        self.P = int(lib.mrl_pop_mlp_num_params(env.kind, self._hid, len(self.hid_sizes)))
         _lib.check(min(self.P, 0), "mrl_pop_mlp_num_params")
 
     def _launch(self, thetas, ld, fs, io):
-        if self.pol is not None:
-            _lib.call("mrl_pop_rollout", ctypes.byref(self.desc), ctypes.byref(self._bufs), ctypes.byref(self.pol),
-                      thetas, ld, fs, ctypes.byref(io), _lib.stream())
-        else:
-            _lib.call("mrl_pop_rollout_mlp", ctypes.byref(self.desc), ctypes.byref(self._bufs), self._hid,
-                      len(self.hid_sizes), thetas, ld, fs, ctypes.byref(io), _lib.stream())
+        entry, net = ("mrl_pop_rollout", (ctypes.byref(self.pol),)) if self.pol is not None else (
+            self.ENTRY, (self._hid, len(self.hid_sizes)))
+        _lib.call(entry, ctypes.byref(self.desc), ctypes.byref(self._bufs), *net, thetas, ld, fs, ctypes.byref(io),
+                  _lib.stream())
 
     @property
     def episodes_started(self):
@@ -362,20 +362,10 @@ class WavePopulationRollout(PopulationRollout):
     ``MrlError`` here."""
 
     DEFAULT_HID = (10, 5)
-
-    def _bind(self, lib):
-        self.pol = None
-        fits = int(lib.mrl_pop_rollout_wave_fits(self.env.kind, self._hid, len(self.hid_sizes)))
-        _lib.check(min(fits, 0), "mrl_pop_rollout_wave_fits")
-        if fits != 1:
-            raise _lib.MrlError(f"WavePopulationRollout: hid_sizes={list(self.hid_sizes)} on {self.env.spec.id} is not "
-                                "a net mrl_pop_rollout_wave takes (Humanoid-v2, at most 3 hidden layers of 1..64 "
-                                "units); envs.population_rollout(env, n, ...) picks the class that serves an env")
-        self._num_params(lib)
-
-    def _launch(self, thetas, ld, fs, io):
-        _lib.call("mrl_pop_rollout_wave", ctypes.byref(self.desc), ctypes.byref(self._bufs), self._hid,
-                  len(self.hid_sizes), thetas, ld, fs, ctypes.byref(io), _lib.stream())
+    ENTRY, FITS, HAS_64_64 = "mrl_pop_rollout_wave", "mrl_pop_rollout_wave_fits", False
+    REFUSAL = ("WavePopulationRollout: hid_sizes={hid} on {env} is not "
+               "a net mrl_pop_rollout_wave takes (Humanoid-v2, at most 3 hidden layers of 1..64 "
+               "units); envs.population_rollout(env, n, ...) picks the class that serves an env")
 
 
 def population_rollout(env, n, *, hid_sizes=None, **kw):

@@ -1,33 +1,29 @@
 """float64 numpy twin of the wave-per-candidate population rollout on Humanoid-v2 (test helper,
-not collected): the policy forward at Humanoid's dims -- ``cem_small_np.forward`` takes
+not collected): the policy forward at Humanoid's dims -- ``cem_np.forward`` takes
 ``[376, ..., 17]`` as it is --, the f32 error bound of the device forward, the test populations
 and the CPU episode twin the replay test's seed was chosen on."""
 import numpy as np
 
-from tests import cem_np, cem_small_np
+from tests import cem_np
 
-ENV_ID, OBS, ACT = "Humanoid-v2", 376, 17
+ENV_ID = "Humanoid-v2"
+OBS, ACT, _ = cem_np.ENVS[ENV_ID]
 U = 2.0 ** -24  # unit roundoff of float32
 
-forward = cem_small_np.forward
+forward = cem_np.forward
 
 
 def dims_of(hid):
-    return [OBS, *[int(h) for h in hid], ACT]
+    return cem_np.dims_of(ENV_ID, hid)
 
 
 def num_params(hid):
-    return cem_small_np.num_params(dims_of(hid), True)
+    return cem_np.num_params(dims_of(hid), True)
 
 
 def population(hid, n, seed, spread=0.1):
     """theta_i = glorot + spread * normal, float32 [n, P]."""
-    from modular_rl_amd import _lib
-    from modular_rl_amd.nets import glorot_init
-    rng = np.random.default_rng(seed)
-    base = glorot_init(rng, OBS, ACT, _lib.HEAD_GAUSS, [int(h) for h in hid])
-    assert base.size == num_params(hid)
-    return (base[None, :] + spread * rng.standard_normal((n, base.size))).astype(np.float32)
+    return cem_np.population(ENV_ID, hid, n, seed, spread)
 
 
 def forward_with_bound(thetas, x, dims, c):
@@ -49,7 +45,7 @@ def forward_with_bound(thetas, x, dims, c):
     z = np.zeros((x.shape[0], dims[-1]))
     tol = np.zeros_like(z)
     for i in range(x.shape[0]):
-        parts = cem_small_np.split_theta(thetas[i], dims)
+        parts = cem_np.split_theta(thetas[i], dims)
         h, e = x[i], U * np.abs(x[i])
         for l, (W, b) in enumerate(parts):
             pre = h @ W + b

@@ -1,6 +1,8 @@
 """float64 numpy twin of the cross-entropy path (test helper, not collected):
 the ``cem`` update (elite order, mean, variance, std schedule), the deterministic policy
-forward on filtered observations, and the per-candidate Welford partial."""
+forward of a tanh MLP of any depth on filtered observations (the 64-64 net is dims
+``[n_in, 64, 64, n_out]``), the env table, the test populations and the per-candidate Welford
+partial."""
 import numpy as np
 
 
@@ -39,11 +41,29 @@ def cem_replay(pops, yss, th_mean, batch_size, elite_frac, initial_std, extra_st
     return out
 
 
-def split_theta(theta, n_in, n_out):
-    """Keras order: W0 [n_in, 64], b0, W1 [64, 64], b1, W2 [64, n_out], b2 (, logstd)."""
+# env -> (obs, act, head is gauss)
+ENVS = {
+    "CartPole-v0": (4, 2, False), "Hopper-v2": (11, 3, True), "Pendulum-v0": (3, 1, True),
+    "MountainCar-v0": (2, 3, False), "Acrobot-v1": (6, 3, False), "InvertedPendulum-v2": (4, 1, True),
+    "InvertedDoublePendulum-v2": (11, 1, True), "Humanoid-v2": (376, 17, True),
+}
+
+
+def dims_of(env_id, hid):
+    O, A, _ = ENVS[env_id]
+    return [O, *[int(h) for h in hid], A]
+
+
+def num_params(dims, gauss):
+    """Keras count: every layer's kernel and bias, plus logstd for a Gauss head."""
+    return sum(dims[l] * dims[l + 1] + dims[l + 1] for l in range(len(dims) - 1)) + (dims[-1] if gauss else 0)
+
+
+def split_theta(theta, dims):
+    """Keras order: W0 [dims[0], dims[1]], b0, W1, b1, ... (, logstd): the (W, b) pairs."""
     th = np.asarray(theta, dtype=np.float64)
     o, parts = 0, []
-    for (r, c) in ((n_in, 64), (64, 64), (64, n_out)):
+    for r, c in zip(dims[:-1], dims[1:]):
         W = th[o:o + r * c].reshape(r, c)
         o += r * c
         b = th[o:o + c]
@@ -64,17 +84,38 @@ def filter_obs(obs, filter_state=None, clip=5.0):
     return np.clip(o, -clip, clip).astype(np.float32).astype(np.float64)
 
 
-def forward(thetas, x, n_out):
-    """Head rows z [N, n_out] of candidate i's net on its row x[i] (thetas [N, P] or [P])."""
+def forward(thetas, x, dims):
+    """Head rows z [N, dims[-1]] of candidate i's net on its row x[i] (thetas [N, P] or [P]);
+    tanh on every hidden layer, none on the head; no hidden layer: x @ W + b."""
     x = np.asarray(x, dtype=np.float64)
     thetas = np.asarray(thetas, dtype=np.float64)
     if thetas.ndim == 1:
         thetas = np.broadcast_to(thetas, (x.shape[0], thetas.size))
-    z = np.zeros((x.shape[0], n_out))
+    z = np.zeros((x.shape[0], dims[-1]))
     for i in range(x.shape[0]):
-        (W0, b0), (W1, b1), (W2, b2) = split_theta(thetas[i], x.shape[1], n_out)
-        z[i] = np.tanh(np.tanh(x[i] @ W0 + b0) @ W1 + b1) @ W2 + b2
+        parts = split_theta(thetas[i], dims)
+        h = x[i]
+        for W, b in parts[:-1]:
+            h = np.tanh(h @ W + b)
+        W, b = parts[-1]
+        z[i] = h @ W + b
     return z
+
+
+def forward_64_64(thetas, x, n_out):
+    """forward at the env's 64-64 net, [n_in, 64, 64, n_out]."""
+    return forward(thetas, x, [np.shape(x)[1], 64, 64, n_out])
+
+
+def population(env_id, hid, n, seed, spread=0.5):
+    """theta_i = glorot + spread * normal, float32 [n, P]."""
+    from modular_rl_amd import _lib
+    from modular_rl_amd.nets import glorot_init
+    O, A, gauss = ENVS[env_id]
+    rng = np.random.default_rng(seed)
+    base = glorot_init(rng, O, A, _lib.HEAD_GAUSS if gauss else _lib.HEAD_SOFTMAX, [int(h) for h in hid])
+    assert base.size == num_params(dims_of(env_id, hid), gauss)
+    return (base[None, :] + spread * rng.standard_normal((n, base.size))).astype(np.float32)
 
 
 def welford_partial(rows):

@@ -130,7 +130,7 @@ def reference_population(env_id):
     for t in range(POP_LIMIT):
         if not alive.any():
             break
-        z = cem_np.forward(th, cem_np.filter_obs(envs.obs()), A)
+        z = cem_np.forward_64_64(th, cem_np.filter_obs(envs.obs()), A)
         rows += int(alive.sum())
         _, done = envs.step(z.astype(np.float32))
         least = min(least, float(margin(envs.kind, envs.state)[alive].min()))

@@ -92,7 +92,7 @@ def reference_population(env_id):
     for t in range(POP_LIMIT):
         if not alive.any():
             break
-        z = cem_np.forward(th, cem_np.filter_obs(envs.obs()), A)
+        z = cem_np.forward_64_64(th, cem_np.filter_obs(envs.obs()), A)
         rows += int(alive.sum())
         if disc:
             srt = np.sort(z, axis=1)

@@ -115,7 +115,7 @@ def reference_population(env_id):
     envs.reset(np.arange(POP_N))
     rows = ended = 0
     for t in range(POP_LIMIT):
-        z = cem_np.forward(th, cem_np.filter_obs(envs.obs()), A)
+        z = cem_np.forward_64_64(th, cem_np.filter_obs(envs.obs()), A)
         rows += POP_N
         _, done = envs.step(z.astype(np.float32))
         ended += int(done.sum())

@@ -2,6 +2,7 @@
 generator (golden), the option table, the C ABI of the new entry points (layout, exports,
 argument checks before any launch) and the command line."""
 import ctypes
+import functools
 import os
 import subprocess
 import sys
@@ -9,7 +10,7 @@ import sys
 import numpy as np
 import pytest
 
-from tests import cem_np
+from tests import cem_np, pop_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "cem.npz")
@@ -67,23 +68,7 @@ def test_pop_io_layout_and_exports(tmp_path):
         assert name in _lib.SIGNATURES
 
 
-def _pop_call(lib, _lib, env=None, n_envs=4, pol=None, ld=None, null=(), io_kw=None, bufs=True):
-    """mrl_pop_rollout with fake non-null pointers (never dereferenced: every check precedes
-    the launch, and every case here fails a check)."""
-    env = _lib.ENV_HOPPER if env is None else env
-    fake = ctypes.c_void_p(0x1000)
-    d = _lib.RolloutDesc(env, n_envs, 1, 0, 0, 0, 0, 0, 0)
-    b = _lib.RolloutBufs(env_state=fake if bufs else None, env_int=fake)
-    pol = pol or _lib.MlpDesc(11, 3, _lib.HEAD_GAUSS, 64, 2)
-    io = _lib.PopIO(fake, fake, fake, fake)
-    for k, v in (io_kw or {}).items():
-        setattr(io, k, v)
-    args = dict(d=ctypes.byref(d), b=ctypes.byref(b), pol=ctypes.byref(pol), thetas=fake, io=ctypes.byref(io))
-    for k in null:
-        args[k] = None
-    rc = lib.mrl_pop_rollout(args["d"], args["b"], args["pol"], args["thetas"], 5126 if ld is None else ld, None,
-                             args["io"], None)
-    return rc, lib.mrl_last_error()
+_pop_call = functools.partial(pop_cases.pop_call, entry="mrl_pop_rollout")
 
 
 def test_pop_rollout_argument_checks():
@@ -110,6 +95,51 @@ def test_pop_rollout_argument_checks():
     for kw in unsupported:
         rc, msg = _pop_call(lib, _lib, **kw)
         assert rc == E_UNSUPPORTED and b"mrl_pop_rollout" in msg, kw
+
+
+def test_the_argument_checks_come_in_one_order_on_all_three_entries():
+    """Calls with two faults each: the first failed check of the ladder names itself, with the
+    entry point's own prefix -- null desc, null bufs, the entry's own check (null policy desc /
+    n_hid < 0, null hid_sizes), null thetas, null io, unknown env, n_envs, bufs.env_state /
+    env_int, io.ret / len / flags / stat, trace_steps, the partly set trace; then the net's
+    shape, then ld_theta."""
+    from modular_rl_amd import _lib
+    lib = _lib.load()
+    fake = ctypes.c_void_p(0x1000)
+    POP, MLP, WAVE = "mrl_pop_rollout", "mrl_pop_rollout_mlp", "mrl_pop_rollout_wave"
+    partly = "the trace is only partly set (trace_steps, trace_obs, trace_act, trace_rew)"
+    for entry in (POP, MLP, WAVE):
+        own = dict(null=("b", "pol")) if entry == POP else dict(null=("b",), n_hid=-1)
+        rows = [(dict(null=("d", "io")), "null desc"),
+                (dict(null=("thetas",), n_envs=0), "null thetas"),
+                (own, "null bufs"),
+                (dict(io_kw=dict(trace_steps=-1, ret=None)), "null io.ret / len / flags / stat"),
+                (dict(io_kw=dict(trace_steps=4, trace_obs=fake), env=3), "desc.env_id: unknown env"),
+                (dict(io_kw=dict(trace_steps=4, trace_obs=fake), n_envs=0), "desc.n_envs <= 0"),
+                (dict(io_kw=dict(trace_steps=4, trace_obs=fake)), partly),
+                (dict(ld=pop_cases.ENTRIES[entry][1] - 1), "ld_theta is neither 0 nor >= the parameter count")]
+        for kw, what in rows:
+            rc, msg = pop_cases.pop_call(lib, _lib, entry, **kw)
+            assert (rc, msg) == (E_ARG, f"{entry}: {what}".encode()), (entry, kw, rc, msg)
+    # the entry's own check sits between null bufs and null thetas
+    for kw, what in ((dict(null=("pol", "thetas")), "mrl_pop_rollout: null policy desc"),):
+        assert pop_cases.pop_call(lib, _lib, POP, **kw) == (E_ARG, what.encode()), kw
+    for entry in (MLP, WAVE):
+        for kw, what in ((dict(n_hid=-1, null_hid=True, null=("thetas",)), "n_hid < 0"),
+                         (dict(n_hid=2, null_hid=True, null=("thetas",)), "null hid_sizes")):
+            assert pop_cases.pop_call(lib, _lib, entry, **kw) == (E_ARG, f"{entry}: {what}".encode()), (entry, kw)
+    # the shape, after the ladder and before ld_theta: each entry's own env test comes before the widths
+    one = [(MLP, dict(env=_lib.ENV_HUMANOID, hid=(65,), ld=1),
+            "mrl_pop_rollout_mlp: Humanoid is not supported (the thread-per-env envs only)"),
+           (WAVE, dict(env=_lib.ENV_HOPPER, hid=(65,), ld=1), "mrl_pop_rollout_wave: the wave-per-env envs only (Humanoid)"),
+           (MLP, dict(hid=(65,), ld=1), "mrl_pop_rollout_mlp: a hidden width outside [1, 64]"),
+           (WAVE, dict(hid=(65,), ld=1), "mrl_pop_rollout_wave: a hidden width outside [1, 64]"),
+           (MLP, dict(hid=(4, 4, 4, 4), ld=1), "mrl_pop_rollout_mlp: more than 3 hidden layers"),
+           (WAVE, dict(hid=(4, 4, 4, 4), ld=1), "mrl_pop_rollout_wave: more than 3 hidden layers"),
+           (POP, dict(env=_lib.ENV_HUMANOID, ld=1),
+            "mrl_pop_rollout: Humanoid is not supported (the thread-per-env envs only)")]
+    for entry, kw, what in one:
+        assert pop_cases.pop_call(lib, _lib, entry, **kw) == (E_UNSUPPORTED, what.encode()), (entry, kw)
 
 
 def test_cem_sample_and_refit_argument_checks():

@@ -2,21 +2,21 @@
 parameter count and the shape predicate of the C ABI, the argument checks before any launch,
 the exports, the command line, and the float64 twin of the forward at Humanoid's dims."""
 import ctypes
+import functools
 import os
 import subprocess
 import sys
 
 import numpy as np
 
-from tests import cem_humanoid_np, cem_small_np
+from tests import cem_humanoid_np, cem_np, pop_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_ARG, E_UNSUPPORTED = -1, -2
 PREFIX = b"mrl_pop_rollout_wave:"
 
 
-def _hid(hid):
-    return (ctypes.c_int32 * max(len(hid), 1))(*hid)
+_hid = pop_cases.hid_array
 
 
 def test_num_params_at_humanoid_dims():
@@ -47,24 +47,7 @@ def test_wave_fits():
     assert lib.mrl_pop_rollout_mlp_fits(HM, _hid((10, 5)), 2) == 0
 
 
-def _wave_call(lib, _lib, env=None, n_envs=4, hid=(10, 5), n_hid=None, null_hid=False, ld=None, null=(), io_kw=None,
-               bufs=True):
-    """mrl_pop_rollout_wave with fake non-null pointers (never dereferenced: every check
-    precedes the launch, and every case here fails a check)."""
-    env = _lib.ENV_HUMANOID if env is None else env
-    fake = ctypes.c_void_p(0x1000)
-    d = _lib.RolloutDesc(env, n_envs, 1, 0, 0, 0, 0, 0, 0)
-    b = _lib.RolloutBufs(env_state=fake if bufs else None, env_int=fake)
-    io = _lib.PopIO(fake, fake, fake, fake)
-    for k, v in (io_kw or {}).items():
-        setattr(io, k, v)
-    args = dict(d=ctypes.byref(d), b=ctypes.byref(b), thetas=fake, io=ctypes.byref(io))
-    for k in null:
-        args[k] = None
-    rc = lib.mrl_pop_rollout_wave(args["d"], args["b"], None if null_hid else _hid(hid),
-                                  len(hid) if n_hid is None else n_hid, args["thetas"], 3944 if ld is None else ld,
-                                  None, args["io"], None)
-    return rc, lib.mrl_last_error()
+_wave_call = functools.partial(pop_cases.pop_call, entry="mrl_pop_rollout_wave")
 
 
 def test_pop_rollout_wave_argument_checks():
@@ -112,7 +95,7 @@ def test_run_cem_help_still_runs():
 
 
 def test_float64_twin_at_humanoid_dims():
-    """cem_small_np.forward takes [376, ..., 17] as it is: against the layers written out, and
+    """cem_np.forward takes [376, ..., 17] as it is: against the layers written out, and
     the error bound is positive, finite and grows with c."""
     rng = np.random.default_rng(0)
     for hid in ((10, 5), (), (7, 3, 5)):
@@ -150,4 +133,4 @@ def test_float64_twin_at_humanoid_dims():
             zf[i] = v
         z32, tol = cem_humanoid_np.forward_with_bound(th.astype(np.float32), h, dims, 2)
         assert np.all(np.abs(zf - z32) <= tol)
-        assert cem_small_np.num_params(dims, True) == P
+        assert cem_np.num_params(dims, True) == P

@@ -2,6 +2,7 @@
 64-64 twin, the zero-padding to 64-64, the parameter count and the LDS predicate of the C ABI,
 the argument checks of mrl_pop_rollout_mlp before any launch, the exports and the command line."""
 import ctypes
+import functools
 import os
 import subprocess
 import sys
@@ -9,7 +10,7 @@ import sys
 import numpy as np
 import pytest
 
-from tests import cem_np, cem_small_np
+from tests import cem_np, cem_small_np, pop_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_ARG, E_UNSUPPORTED = -1, -2
@@ -22,18 +23,26 @@ def _ids(_lib):
             "InvertedPendulum-v2": _lib.ENV_INVPENDULUM, "InvertedDoublePendulum-v2": _lib.ENV_INVDOUBLEPENDULUM}
 
 
-def _hid(hid):
-    return (ctypes.c_int32 * max(len(hid), 1))(*hid)
+_hid = pop_cases.hid_array
 
 
 def test_forward_at_64_64_is_the_64_64_twin():
+    """The general forward at [11, 64, 64, 3] against the three layers written out."""
     rng = np.random.default_rng(0)
-    P = cem_small_np.num_params([11, 64, 64, 3], True)
+    P = cem_np.num_params([11, 64, 64, 3], True)
     assert P == 5126
     th = rng.standard_normal((6, P))
     x = rng.standard_normal((6, 11))
-    assert np.array_equal(cem_small_np.forward(th, x, [11, 64, 64, 3]), cem_np.forward(th, x, 3))
-    assert np.array_equal(cem_small_np.forward(th[0], x, [11, 64, 64, 3]), cem_np.forward(th[0], x, 3))
+
+    def written_out(t, r):
+        W0, b0 = t[0:704].reshape(11, 64), t[704:768]
+        W1, b1 = t[768:4864].reshape(64, 64), t[4864:4928]
+        W2, b2 = t[4928:5120].reshape(64, 3), t[5120:5123]
+        return np.tanh(np.tanh(r @ W0 + b0) @ W1 + b1) @ W2 + b2
+
+    assert np.array_equal(cem_np.forward(th, x, [11, 64, 64, 3]), np.stack([written_out(th[i], x[i]) for i in range(6)]))
+    assert np.array_equal(cem_np.forward(th[0], x, [11, 64, 64, 3]), np.stack([written_out(th[0], r) for r in x]))
+    assert np.array_equal(cem_np.forward_64_64(th, x, 3), cem_np.forward(th, x, [11, 64, 64, 3]))
     # no hidden layer: x @ W + b
     W, b = rng.standard_normal((4, 2)), rng.standard_normal(2)
     lin = cem_small_np.forward(np.concatenate([W.ravel(), b]), x[:, :4], [4, 2])
@@ -52,10 +61,10 @@ def test_padded_net_computes_the_small_net(n_in, n_out, gauss):
     x = rng.standard_normal((5, n_in))
     pad = np.stack([cem_small_np.pad_to_64_64(t, n_in, (10, 5), n_out, gauss) for t in th])
     assert pad.dtype == np.float32 and pad.shape == (5, cem_small_np.num_params([n_in, 64, 64, n_out], gauss))
-    np.testing.assert_allclose(cem_np.forward(pad, x, n_out), cem_small_np.forward(th, x, dims), rtol=1e-13, atol=1e-15)
+    np.testing.assert_allclose(cem_np.forward_64_64(pad, x, n_out), cem_small_np.forward(th, x, dims), rtol=1e-13, atol=1e-15)
     if gauss:
         assert np.array_equal(pad[:, -n_out:], th[:, -n_out:])
-    (W0, _), (W1, _), _ = cem_np.split_theta(pad[0], n_in, n_out)
+    (W0, _), (W1, _), _ = cem_np.split_theta(pad[0], [n_in, 64, 64, n_out])
     assert not W0[:, 10:].any() and not W1[10:, :].any() and not W1[:, 5:].any()
 
 
@@ -88,24 +97,7 @@ def test_num_params_and_fits():
     assert lib.mrl_pop_mlp_num_params(7, _hid((10, 5)), 2) == E_ARG
 
 
-def _pop_call(lib, _lib, env=None, n_envs=4, hid=(10, 5), n_hid=None, null_hid=False, ld=None, null=(), io_kw=None,
-              bufs=True):
-    """mrl_pop_rollout_mlp with fake non-null pointers (never dereferenced: every check
-    precedes the launch, and every case here fails a check)."""
-    env = _lib.ENV_HOPPER if env is None else env
-    fake = ctypes.c_void_p(0x1000)
-    d = _lib.RolloutDesc(env, n_envs, 1, 0, 0, 0, 0, 0, 0)
-    b = _lib.RolloutBufs(env_state=fake if bufs else None, env_int=fake)
-    io = _lib.PopIO(fake, fake, fake, fake)
-    for k, v in (io_kw or {}).items():
-        setattr(io, k, v)
-    args = dict(d=ctypes.byref(d), b=ctypes.byref(b), thetas=fake, io=ctypes.byref(io))
-    for k in null:
-        args[k] = None
-    rc = lib.mrl_pop_rollout_mlp(args["d"], args["b"], None if null_hid else _hid(hid),
-                                 len(hid) if n_hid is None else n_hid, args["thetas"], 196 if ld is None else ld, None,
-                                 args["io"], None)
-    return rc, lib.mrl_last_error()
+_pop_call = functools.partial(pop_cases.pop_call, entry="mrl_pop_rollout_mlp")
 
 
 def test_pop_rollout_mlp_argument_checks():

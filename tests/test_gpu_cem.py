@@ -5,34 +5,22 @@ import numpy as np
 import pytest
 import torch
 
-from tests import cem_np
+from tests import cem_np, pop_cases
 
 pytestmark = pytest.mark.gpu
 
-# env -> (obs, act, head is gauss)
-SHAPES = {"Hopper-v2": (11, 3, True), "CartPole-v0": (4, 2, False)}
+HID = (64, 64)  # mrl_pop_rollout
 # seed 24: the float64 twin on the CPU oracle envs ends 61 episodes early and cuts 9 at the limit
 HOPPER_SEED, HOPPER_N, HOPPER_LIMIT = 24, 70, 40
 CARTPOLE_SEED, CARTPOLE_N = 5, 7
 
 
 def population(env_id, n, seed, spread=0.5):
-    """theta_i = glorot + spread * normal, float32 [n, P]."""
-    from modular_rl_amd import _lib
-    from modular_rl_amd.nets import glorot_init
-    O, A, gauss = SHAPES[env_id]
-    rng = np.random.default_rng(seed)
-    base = glorot_init(rng, O, A, _lib.HEAD_GAUSS if gauss else _lib.HEAD_SOFTMAX)
-    return (base[None, :] + spread * rng.standard_normal((n, base.size))).astype(np.float32)
+    return cem_np.population(env_id, HID, n, seed, spread)
 
 
 def run_traced(env_id, n, seed, limit, thetas, filter_state=None, shared=False):
-    from modular_rl_amd.envs import PopulationRollout
-    pop = PopulationRollout(env_id, n, seed=seed, timestep_limit=limit)
-    th = torch.as_tensor(thetas).cuda()
-    out = (pop.evaluate if shared else pop)(th, filter_state=filter_state, trace_steps=pop.limit)
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy().copy() for k, v in out.items()}, pop
+    return pop_cases.run_traced(env_id, HID, n, seed, limit, thetas, filter_state, shared)
 
 
 @pytest.fixture(scope="module")
@@ -49,86 +37,23 @@ def cartpole_run():
     return th, out
 
 
-def check_replay(env_id, n, seed, out, limit):
-    """The traced actions through a VecEnv (same seed, no auto-reset) give the traced raw
-    observations and rewards bit for bit, the same length and terminated bit; ret is the
-    fp64 step-order sum of the traced rewards; stat is the Welford partial of the rows."""
-    from modular_rl_amd.envs import VecEnv
-    O = SHAPES[env_id][0]
-    env = VecEnv(env_id, n, seed=seed, auto_reset=False)
-    obs = env.reset().cpu().numpy().copy()
-    L = out["len"]
-    assert L.min() >= 1 and L.max() <= limit
-    alive = np.ones(n, dtype=bool)
-    ret = [0.0] * n
-    for t in range(int(L.max())):
-        assert np.array_equal(obs[alive], out["trace_obs"][t][alive]), t
-        ob, rew, done, info = env.step(torch.as_tensor(out["trace_act"][t]).cuda())
-        obs, rew = ob.cpu().numpy().copy(), rew.cpu().numpy()
-        term = info["terminated"].cpu().numpy()
-        assert np.array_equal(rew[alive], out["trace_rew"][t][alive]), t
-        for i in np.nonzero(alive)[0]:
-            ret[i] += float(out["trace_rew"][t][i])
-            ended = term[i] or t + 1 >= limit
-            assert ended == (L[i] == t + 1), (t, i)
-            if ended:
-                assert bool(out["flags"][i] & 2) == bool(term[i]), (t, i)
-                alive[i] = False
-    assert not alive.any()
-    assert np.array_equal(np.array(ret), out["ret"])
-    for i in range(n):
-        want = cem_np.welford_partial(out["trace_obs"][:L[i], i])
-        np.testing.assert_allclose(out["stat"][i], want, rtol=1e-9, atol=0, err_msg=str(i))
-        assert out["stat"][i].shape == (1 + 2 * O,)
-
-
 def test_hopper_replay(hopper_run):
     _, out = hopper_run
     term = (out["flags"] & 2) != 0
     print("hopper: terminated", int(term.sum()), "cut at the limit", int((~term).sum()), "len", out["len"].tolist())
     assert term.sum() >= 5 and (~term).sum() >= 5
     assert np.all(out["len"][~term] == HOPPER_LIMIT)
-    check_replay("Hopper-v2", HOPPER_N, HOPPER_SEED, out, HOPPER_LIMIT)
+    pop_cases.check_replay("Hopper-v2", HOPPER_N, HOPPER_SEED, out, HOPPER_LIMIT)
 
 
 def test_cartpole_replay(cartpole_run):
     _, out = cartpole_run
-    check_replay("CartPole-v0", CARTPOLE_N, CARTPOLE_SEED, out, 200)
+    pop_cases.check_replay("CartPole-v0", CARTPOLE_N, CARTPOLE_SEED, out, 200)
     assert np.array_equal(out["ret"], out["len"].astype(np.float64))
 
 
-def filter_state_for(env_id, rows):
-    """A BatchZFilter state after a few hundred traced observation rows (n >= 2)."""
-    from modular_rl_amd.filters import BatchZFilter
-    O = SHAPES[env_id][0]
-    f = BatchZFilter(O, len(rows))
-    f(torch.as_tensor(rows).cuda(), update=True)
-    torch.cuda.synchronize()
-    assert f.n >= 2
-    return f.state.clone()
-
-
 def check_actions(env_id, thetas, out, filter_state):
-    """Every traced (raw obs, action) pair against the float64 forward."""
-    O, A, gauss = SHAPES[env_id]
-    fs = None if filter_state is None else filter_state.cpu().numpy()
-    L = out["len"]
-    rows, skipped = 0, 0
-    for t in range(int(L.max())):
-        live = np.nonzero(L > t)[0]
-        x = cem_np.filter_obs(out["trace_obs"][t][live], fs)
-        z = cem_np.forward(np.asarray(thetas, dtype=np.float64)[live] if np.ndim(thetas) == 2 else thetas, x, A)
-        rows += len(live)
-        if gauss:
-            np.testing.assert_allclose(out["trace_act"][t][live], z, rtol=1e-4, atol=1e-5, err_msg=str(t))
-        else:
-            srt = np.sort(z, axis=1)
-            clear = (srt[:, -1] - srt[:, -2]) >= 1e-4
-            skipped += int((~clear).sum())
-            assert np.array_equal(out["trace_act"][t][live][clear], np.argmax(z, axis=1)[clear]), t
-    print(env_id, "rows", rows, "skipped (top-two logits closer than 1e-4)", skipped)
-    assert skipped <= 0.01 * rows
-    return rows, skipped
+    return pop_cases.check_actions(env_id, HID, thetas, out, filter_state)
 
 
 @pytest.mark.parametrize("env_id", ["Hopper-v2", "CartPole-v0"])
@@ -141,9 +66,9 @@ def test_actions_against_float64(env_id, hopper_run, cartpole_run):
     src = raw
     if not hopper:  # seven random CartPole policies give a few dozen rows: take them from a wider run
         src, _ = run_traced(env_id, 64, CARTPOLE_SEED + 1, 0, population(env_id, 64, CARTPOLE_SEED + 1))
-    rows = np.concatenate([src["trace_obs"][t][src["len"] > t] for t in range(int(src["len"].max()))])[:400]
+    rows = pop_cases.traced_rows(src)
     assert len(rows) >= 300
-    fs = filter_state_for(env_id, rows)
+    fs = pop_cases.filter_state_for(env_id, rows)
     out, _ = run_traced(env_id, n, seed, limit, th, filter_state=fs)
     # rows skipped for near-tied logits when this was written: CartPole 0 of 67 raw and 0 of 135 filtered
     check_actions(env_id, th, out, fs)
@@ -156,7 +81,7 @@ def test_shared_theta_equals_copies(env_id):
     th = population(env_id, 1, 11, spread=0.1)[0]
     a, _ = run_traced(env_id, n, 4, 25, th, shared=True)
     b, _ = run_traced(env_id, n, 4, 25, np.repeat(th[None, :], n, axis=0))
-    for k in ("ret", "len", "flags", "stat", "trace_obs", "trace_act", "trace_rew"):
+    for k in pop_cases.KEYS:
         assert np.array_equal(a[k], b[k]), k
 
 
@@ -344,7 +269,7 @@ def test_deterministic_agent_acts_filters_and_snapshots(tmp_path):
     x = agent.obfilt(ob)
     np.testing.assert_allclose(x, cem_np.filter_obs(ob[None], fs)[0], rtol=1e-6, atol=1e-7)  # the twin rounds to f32
     act, info = agent.act(x)
-    z = cem_np.forward(agent.get_flat(), x.astype(np.float32)[None], 3)[0]
+    z = cem_np.forward_64_64(agent.get_flat(), x.astype(np.float32)[None], 3)[0]
     np.testing.assert_allclose(act, z, rtol=1e-4, atol=1e-5)
     assert agent.rewfilt(2.5) == 2.5
     path = save_snapshot(str(tmp_path / "det.npz"), agent, 7, "Hopper-v2")

@@ -14,7 +14,8 @@ import pytest
 import torch
 
 from tests import cem_humanoid_np as HN
-from tests import cem_np
+from tests import cem_np, pop_cases
+from tests.pop_cases import KEYS
 
 pytestmark = pytest.mark.gpu
 
@@ -24,23 +25,19 @@ ENV = HN.ENV_ID
 # ends 36 episodes by itself (lengths 14 .. 24) and cuts 34 at the limit; of seeds 40 .. 51 the
 # one (with 44) furthest from the floor of 5 on both sides
 HM_SEED, HM_N, HM_LIMIT, HM_SPREAD = 46, 70, 24, 0.1
-KEYS = ("ret", "len", "flags", "stat", "trace_obs", "trace_act", "trace_rew")
-# The action tolerance is cem_humanoid_np.forward_with_bound's: per output the f32 accumulation
-# bound c (din + 2) u (sum |x W| + |b|), u = 2^-24, carried through the layers.  c = 1 is the
-# first-order bound of din products, din - 1 sums and the bias in any order; c = 2 covers what
-# first order leaves out -- gamma_n = n u / (1 - n u) against n u, the products of an input's
-# error with a rounding error -- and the float64 twin's own rounding (2^-53 per operation), all
-# far below one more first-order term.
-C_BOUND = 2
 
 
 def run_traced(hid, n, seed, limit, thetas, filter_state=None, shared=False):
     from modular_rl_amd.envs import WavePopulationRollout
-    pop = WavePopulationRollout(ENV, n, seed=seed, timestep_limit=limit, hid_sizes=hid)
-    th = torch.as_tensor(thetas).cuda()
-    out = (pop.evaluate if shared else pop)(th, filter_state=filter_state, trace_steps=pop.limit)
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy().copy() for k, v in out.items()}, pop
+    return pop_cases.run_traced(ENV, hid, n, seed, limit, thetas, filter_state, shared, cls=WavePopulationRollout)
+
+
+def check_replay(n, seed, out, limit):
+    pop_cases.check_replay(ENV, n, seed, out, limit)
+
+
+def check_actions(hid, thetas, out, filter_state):
+    return pop_cases.check_actions_bound(ENV, hid, thetas, out, filter_state)
 
 
 @pytest.fixture(scope="module")
@@ -54,81 +51,10 @@ def hm_run():
 @pytest.fixture(scope="module")
 def hm_filter(hm_run):
     """A BatchZFilter state after 400 traced observation rows of the 10-5 run."""
-    from modular_rl_amd.filters import BatchZFilter
     _, raw = hm_run
-    rows = np.concatenate([raw["trace_obs"][t][raw["len"] > t] for t in range(int(raw["len"].max()))])[:400]
+    rows = pop_cases.traced_rows(raw)
     assert len(rows) >= 300
-    f = BatchZFilter(HN.OBS, len(rows))
-    f(torch.as_tensor(rows).cuda(), update=True)
-    torch.cuda.synchronize()
-    assert f.n >= 2
-    return f.state.clone()
-
-
-def check_replay(n, seed, out, limit):
-    """test_gpu_cem_small.check_replay at Humanoid's dims: the traced actions through a VecEnv
-    (same seed, no auto-reset) give the traced raw observations and rewards bit for bit, the
-    same length and terminated bit; ret is the fp64 step-order sum of the traced rewards; stat
-    is the Welford partial of the rows."""
-    from modular_rl_amd.envs import VecEnv
-    env = VecEnv(ENV, n, seed=seed, auto_reset=False)
-    obs = env.reset().cpu().numpy().copy()
-    L = out["len"]
-    assert L.min() >= 1 and L.max() <= limit
-    alive = np.ones(n, dtype=bool)
-    ret = [0.0] * n
-    for t in range(int(L.max())):
-        assert np.array_equal(obs[alive], out["trace_obs"][t][alive]), t
-        ob, rew, done, info = env.step(torch.as_tensor(out["trace_act"][t]).cuda())
-        obs, rew = ob.cpu().numpy().copy(), rew.cpu().numpy()
-        term = info["terminated"].cpu().numpy()
-        assert np.array_equal(rew[alive], out["trace_rew"][t][alive]), t
-        for i in np.nonzero(alive)[0]:
-            ret[i] += float(out["trace_rew"][t][i])
-            ended = term[i] or t + 1 >= limit
-            assert ended == (L[i] == t + 1), (t, i)
-            if ended:
-                assert bool(out["flags"][i] & 2) == bool(term[i]), (t, i)
-                alive[i] = False
-    assert not alive.any()
-    assert np.array_equal(np.array(ret), out["ret"])
-    assert np.all(out["flags"] & 1)
-    O = HN.OBS
-    for i in range(n):
-        rows = out["trace_obs"][:L[i], i]
-        want = cem_np.welford_partial(rows)
-        # A column that is exactly constant over the episode (the bodies' masses in cinert, the
-        # world body's zeros): its exact partial is known -- mean the value, M2 0 -- and Welford's
-        # recurrence gives exactly that (dlt = 0 from the second row on), while the two-pass twin
-        # rounds the mean of n equal values and returns M2 ~ 1e-28 for 0, which no rtol with
-        # atol 0 takes.  Those entries are held to the exact value, bit for bit; every other
-        # entry to the two-pass twin at rtol 1e-9.
-        const = np.ptp(rows, axis=0) == 0
-        want[1:1 + O][const] = rows[0][const]
-        want[1 + O:][const] = 0.0
-        assert np.array_equal(out["stat"][i][1:1 + O][const], rows[0][const]), i
-        assert not out["stat"][i][1 + O:][const].any(), i
-        np.testing.assert_allclose(out["stat"][i], want, rtol=1e-9, atol=0, err_msg=str(i))
-        assert out["stat"][i].shape == (1 + 2 * HN.OBS,)
-
-
-def check_actions(hid, thetas, out, filter_state):
-    """Every traced (raw obs, action) row against the float64 forward, within the derived bound."""
-    dims = HN.dims_of(hid)
-    fs = None if filter_state is None else filter_state.cpu().numpy()
-    L = out["len"]
-    th64 = np.asarray(thetas, dtype=np.float64)
-    rows, worst = 0, 0.0
-    for t in range(int(L.max())):
-        live = np.nonzero(L > t)[0]
-        x = cem_np.filter_obs(out["trace_obs"][t][live], fs)
-        z, tol = HN.forward_with_bound(th64[live] if th64.ndim == 2 else th64, x, dims, C_BOUND)
-        err = np.abs(out["trace_act"][t][live].astype(np.float64) - z)
-        rows += len(live)
-        worst = max(worst, float((err / tol).max()))
-        assert np.all(err <= tol), (t, float((err / tol).max()))
-    print(ENV, list(hid), "filtered" if fs is not None else "raw", "rows", rows, "worst error / bound", worst)
-    return rows
+    return pop_cases.filter_state_for(ENV, rows)
 
 
 def test_replay(hm_run):

@@ -11,74 +11,31 @@ import numpy as np
 import pytest
 import torch
 
-from tests import cem_np, cem_small_np
+from tests import cem_np, cem_small_np, pop_cases
+from tests.pop_cases import KEYS, check_actions, check_replay, run_traced
 
 pytestmark = pytest.mark.gpu
 
-ENVS = cem_small_np.ENVS
-# seed 30: the float64 twin on the CPU oracle envs (oracle/rollout_np.Envs, cem_small_np.forward
+ENVS = cem_np.ENVS
+# seed 30: the float64 twin on the CPU oracle envs (oracle/rollout_np.Envs, cem_np.forward
 # on the clipped observations) ends 60 episodes early and cuts 10 at the limit (of seeds 20 .. 39
 # the one furthest from the floor of 5 on both sides)
 HOPPER_SEED, HOPPER_N, HOPPER_LIMIT = 30, 70, 40
 CARTPOLE_SEED, CARTPOLE_N = 5, 7
-KEYS = ("ret", "len", "flags", "stat", "trace_obs", "trace_act", "trace_rew")
-
-
-def run_traced(env_id, hid, n, seed, limit, thetas, filter_state=None, shared=False):
-    from modular_rl_amd.envs import PopulationRollout
-    pop = PopulationRollout(env_id, n, seed=seed, timestep_limit=limit, hid_sizes=hid)
-    th = torch.as_tensor(thetas).cuda()
-    out = (pop.evaluate if shared else pop)(th, filter_state=filter_state, trace_steps=pop.limit)
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy().copy() for k, v in out.items()}, pop
 
 
 @pytest.fixture(scope="module")
 def hopper_run():
-    th = cem_small_np.population("Hopper-v2", (10, 5), HOPPER_N, HOPPER_SEED)
+    th = cem_np.population("Hopper-v2", (10, 5), HOPPER_N, HOPPER_SEED)
     out, _ = run_traced("Hopper-v2", (10, 5), HOPPER_N, HOPPER_SEED, HOPPER_LIMIT, th)
     return th, out
 
 
 @pytest.fixture(scope="module")
 def cartpole_run():
-    th = cem_small_np.population("CartPole-v0", (10, 5), CARTPOLE_N, CARTPOLE_SEED)
+    th = cem_np.population("CartPole-v0", (10, 5), CARTPOLE_N, CARTPOLE_SEED)
     out, _ = run_traced("CartPole-v0", (10, 5), CARTPOLE_N, CARTPOLE_SEED, 0, th)
     return th, out
-
-
-def check_replay(env_id, n, seed, out, limit):
-    """The traced actions through a VecEnv (same seed, no auto-reset) give the traced raw
-    observations and rewards bit for bit, the same length and terminated bit; ret is the
-    fp64 step-order sum of the traced rewards; stat is the Welford partial of the rows."""
-    from modular_rl_amd.envs import VecEnv
-    O = ENVS[env_id][0]
-    env = VecEnv(env_id, n, seed=seed, auto_reset=False)
-    obs = env.reset().cpu().numpy().copy()
-    L = out["len"]
-    assert L.min() >= 1 and L.max() <= limit
-    alive = np.ones(n, dtype=bool)
-    ret = [0.0] * n
-    for t in range(int(L.max())):
-        assert np.array_equal(obs[alive], out["trace_obs"][t][alive]), t
-        ob, rew, done, info = env.step(torch.as_tensor(out["trace_act"][t]).cuda())
-        obs, rew = ob.cpu().numpy().copy(), rew.cpu().numpy()
-        term = info["terminated"].cpu().numpy()
-        assert np.array_equal(rew[alive], out["trace_rew"][t][alive]), t
-        for i in np.nonzero(alive)[0]:
-            ret[i] += float(out["trace_rew"][t][i])
-            ended = term[i] or t + 1 >= limit
-            assert ended == (L[i] == t + 1), (t, i)
-            if ended:
-                assert bool(out["flags"][i] & 2) == bool(term[i]), (t, i)
-                alive[i] = False
-    assert not alive.any()
-    assert np.array_equal(np.array(ret), out["ret"])
-    assert np.all(out["flags"] & 1)
-    for i in range(n):
-        want = cem_np.welford_partial(out["trace_obs"][:L[i], i])
-        np.testing.assert_allclose(out["stat"][i], want, rtol=1e-9, atol=0, err_msg=str(i))
-        assert out["stat"][i].shape == (1 + 2 * O,)
 
 
 def test_hopper_replay(hopper_run):
@@ -96,43 +53,6 @@ def test_cartpole_replay(cartpole_run):
     assert np.array_equal(out["ret"], out["len"].astype(np.float64))
 
 
-def filter_state_for(env_id, rows):
-    """A BatchZFilter state after a few hundred traced observation rows (n >= 2)."""
-    from modular_rl_amd.filters import BatchZFilter
-    O = ENVS[env_id][0]
-    f = BatchZFilter(O, len(rows))
-    f(torch.as_tensor(rows).cuda(), update=True)
-    torch.cuda.synchronize()
-    assert f.n >= 2
-    return f.state.clone()
-
-
-def check_actions(env_id, hid, thetas, out, filter_state):
-    """Every traced (raw obs, action) pair against the float64 forward."""
-    O, A, gauss = ENVS[env_id]
-    dims = cem_small_np.dims_of(env_id, hid)
-    fs = None if filter_state is None else filter_state.cpu().numpy()
-    L = out["len"]
-    rows, skipped = 0, 0
-    th64 = np.asarray(thetas, dtype=np.float64)
-    for t in range(int(L.max())):
-        live = np.nonzero(L > t)[0]
-        x = cem_np.filter_obs(out["trace_obs"][t][live], fs)
-        z = cem_small_np.forward(th64[live], x, dims)
-        rows += len(live)
-        if gauss:
-            np.testing.assert_allclose(out["trace_act"][t][live], z, rtol=1e-4, atol=1e-5, err_msg=str(t))
-        else:
-            srt = np.sort(z, axis=1)
-            clear = (srt[:, -1] - srt[:, -2]) >= 1e-4
-            skipped += int((~clear).sum())
-            assert np.array_equal(out["trace_act"][t][live][clear], np.argmax(z, axis=1)[clear]), t
-    print(env_id, list(hid), "filtered" if fs is not None else "raw", "rows", rows,
-          "skipped (top-two logits closer than 1e-4)", skipped)
-    assert skipped <= 0.01 * rows
-    return rows, skipped
-
-
 # populations of spread 0.5 put the top two logits O(0.1 .. 1) apart: a gap below 1e-4 is a
 # 1e-4 .. 1e-3 event per row, far below the 1 % cap (the counts are printed)
 @pytest.mark.parametrize("env_id,hid", [
@@ -146,13 +66,13 @@ def test_actions_against_float64(env_id, hid, hopper_run):
         n, seed, limit = HOPPER_N, HOPPER_SEED, HOPPER_LIMIT
         th, raw = hopper_run
     else:
-        th = cem_small_np.population(env_id, hid, n, seed)
+        th = cem_np.population(env_id, hid, n, seed)
         raw, pop = run_traced(env_id, hid, n, seed, limit, th)
         assert pop.P == th.shape[1]
     check_actions(env_id, hid, th, raw, None)  # the pass-through branch (filter_state None)
-    rows = np.concatenate([raw["trace_obs"][t][raw["len"] > t] for t in range(int(raw["len"].max()))])[:400]
+    rows = pop_cases.traced_rows(raw)
     assert len(rows) >= 300
-    fs = filter_state_for(env_id, rows)
+    fs = pop_cases.filter_state_for(env_id, rows)
     out, _ = run_traced(env_id, hid, n, seed, limit, th, filter_state=fs)
     check_actions(env_id, hid, th, out, fs)
     assert not np.array_equal(out["trace_act"], raw["trace_act"])  # the filter is live
@@ -170,7 +90,7 @@ def test_bit_identity_with_the_64_64_kernel(env_id, hopper_run):
     if gauss:
         th, small = hopper_run
     else:
-        th = cem_small_np.population(env_id, (10, 5), n, seed)
+        th = cem_np.population(env_id, (10, 5), n, seed)
         small, _ = run_traced(env_id, (10, 5), n, seed, limit, th)
     pad = np.stack([cem_small_np.pad_to_64_64(t, O, (10, 5), A, gauss) for t in th])
     pop = PopulationRollout(env_id, n, seed=seed, timestep_limit=limit)  # hid_sizes (64, 64): mrl_pop_rollout
@@ -185,7 +105,7 @@ def test_bit_identity_with_the_64_64_kernel(env_id, hopper_run):
 @pytest.mark.parametrize("env_id", ["Hopper-v2", "CartPole-v0"])
 def test_shared_theta_equals_copies(env_id):
     n = 70
-    th = cem_small_np.population(env_id, (10, 5), 1, 11, spread=0.1)[0]
+    th = cem_np.population(env_id, (10, 5), 1, 11, spread=0.1)[0]
     a, _ = run_traced(env_id, (10, 5), n, 4, 25, th, shared=True)
     b, _ = run_traced(env_id, (10, 5), n, 4, 25, np.repeat(th[None, :], n, axis=0))
     for k in KEYS:
@@ -217,7 +137,7 @@ def test_row_stride_through_the_c_entry(hopper_run):
 
 def test_two_calls_give_the_same_bits():
     from modular_rl_amd.envs import PopulationRollout
-    th = torch.as_tensor(cem_small_np.population("Hopper-v2", (10, 5), 70, 2)).cuda()
+    th = torch.as_tensor(cem_np.population("Hopper-v2", (10, 5), 70, 2)).cuda()
     pop = PopulationRollout("Hopper-v2", 70, seed=9, timestep_limit=30, hid_sizes=(10, 5))
     first = {k: v.clone() for k, v in pop(th).items()}
     assert int(pop.episodes_started.min()) == 1
@@ -231,7 +151,7 @@ def test_two_calls_give_the_same_bits():
 
 @pytest.mark.parametrize("env_id,hid", [("Hopper-v2", (10, 5)), ("CartPole-v0", ())])
 def test_one_candidate_runs_and_replays(env_id, hid):
-    th = cem_small_np.population(env_id, hid, 1, 3, spread=0.2)
+    th = cem_np.population(env_id, hid, 1, 3, spread=0.2)
     out, _ = run_traced(env_id, hid, 1, 6, 30, th)
     check_replay(env_id, 1, 6, out, 30)
     check_actions(env_id, hid, th, out, None)
@@ -306,7 +226,7 @@ def test_deterministic_agent_10_5_acts_and_snapshots(tmp_path):
     agent.filter_state.copy_(torch.as_tensor(fs))
     x = agent.obfilt(ob)
     act, _ = agent.act(x)
-    z = cem_small_np.forward(th, x.astype(np.float32)[None], [11, 10, 5, 3])[0]
+    z = cem_np.forward(th, x.astype(np.float32)[None], [11, 10, 5, 3])[0]
     np.testing.assert_allclose(act, z, rtol=1e-4, atol=1e-5)
     path = save_snapshot(str(tmp_path / "det.npz"), agent, 7, "Hopper-v2")
     other = DeterministicAgent(env.observation_space, env.action_space, dict(seed=2, hid_sizes=[10, 5]))

@@ -274,7 +274,7 @@ def test_population_rollout_replays_through_a_vecenv(env_id):
             break
         np.testing.assert_allclose(obs[alive], out["trace_obs"][t][alive], rtol=1e-5, atol=1e-5, err_msg=f"obs {t}")
         if disc:  # the traced action is the float64 arg-max wherever the top two logits are apart
-            z = cem_np.forward(thetas.astype(np.float64)[alive], cem_np.filter_obs(out["trace_obs"][t][alive]), A)
+            z = cem_np.forward_64_64(thetas.astype(np.float64)[alive], cem_np.filter_obs(out["trace_obs"][t][alive]), A)
             srt = np.sort(z, axis=1)
             ok = (srt[:, -1] - srt[:, -2]) > 1e-4
             rows, clear = rows + len(z), clear + int(ok.sum())
