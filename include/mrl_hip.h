@@ -290,6 +290,27 @@ typedef struct {
   int32_t lds_limit;    /* as mrl_gemm_bf16_desc.lds_limit */
 } mrl_gemm_bf16_tn_desc;
 int mrl_gemm_bf16_tn(const mrl_gemm_bf16_tn_desc* g, const int32_t* skip, void* stream);
+/* The kernel mrl_gemm_bf16 / mrl_gemm_bf16_tn launches for a descriptor on the current
+ * device, by the decision the launch itself takes (the same environment overrides, the
+ * same CU count): host-only queries that launch nothing and read no operand.  INVALID: a
+ * null descriptor; NONE: an empty product (m or n <= 0). */
+enum {
+  MRL_GEMM_ROUTE_INVALID = -1,
+  MRL_GEMM_ROUTE_NONE = 0,
+  MRL_GEMM_ROUTE_TILED128_BK64 = 1, /* 128 x 128 tiles, 64-deep K stages */
+  MRL_GEMM_ROUTE_TILED128_BK32 = 2, /* ... 32-deep (lds_limit)           */
+  MRL_GEMM_ROUTE_TILED32_BK64 = 3,  /* 128 x 32 tiles (n <= 32)          */
+  MRL_GEMM_ROUTE_TILED32_BK32 = 4,
+  MRL_GEMM_ROUTE_SMALL = 5,         /* 64 x 64 whole-K LDS-DMA           */
+  MRL_GEMM_ROUTE_STREAM384 = 6,     /* streaming, K plan 384             */
+  MRL_GEMM_ROUTE_STREAM512 = 7,
+  MRL_GEMM_ROUTE_BIG = 8,           /* 256 x 256 LDS-DMA                 */
+  MRL_GEMM_ROUTE_TN_TILED32 = 9,
+  MRL_GEMM_ROUTE_TN_TILED128 = 10,
+  MRL_GEMM_ROUTE_TN_BIG = 11        /* 256 x 256 TN, transposing reads   */
+};
+int32_t mrl_gemm_bf16_route(const mrl_gemm_bf16_desc* g);
+int32_t mrl_gemm_bf16_tn_route(const mrl_gemm_bf16_tn_desc* g);
 /* y[r, c] = bf16(x[r, c]) (RNE) for c < cols, 0 for cols <= c < ldy */
 int mrl_cast_rows_bf16(const float* x, int64_t rows, int64_t cols, int64_t ldx, uint16_t* y, int64_t ldy,
                        void* stream);

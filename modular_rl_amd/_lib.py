@@ -131,6 +131,8 @@ SIGNATURES = {
     "mrl_gemm_tile_n": (i32, [vp]),
     "mrl_gemm_bf16": (i32, [vp, vp, vp]),
     "mrl_gemm_bf16_tn": (i32, [vp, vp, vp]),
+    "mrl_gemm_bf16_route": (i32, [vp]),
+    "mrl_gemm_bf16_tn_route": (i32, [vp]),
     "mrl_cast_rows_bf16": (i32, [vp, i64, i64, i64, vp, i64, vp]),
     "mrl_pack_w_bf16": (i32, [vp, i64, i64, i32, vp, i64, vp]),
     "mrl_colsum": (i32, [vp, i64, i64, i64, i32, vp, i64, vp, vp]),

@@ -312,11 +312,12 @@ __global__ void pack_w_bf16_kernel(const float* __restrict__ w, int64_t din, int
   }
 }
 
-// the tiled kernel with QBK-deep K stages: 128 x 32 tiles for N <= 32, else 128 x 128
+// the tiled kernel with QBK-deep K stages: 128 x 32 tiles (`narrow`: nn_route sends
+// N <= 32 there), else 128 x 128
 template <int QBK>
-static void launch_tiled(const GemmB16Args& g, bool bf, hipStream_t s) {
+static void launch_tiled(const GemmB16Args& g, bool narrow, bool bf, hipStream_t s) {
   const unsigned gm = (unsigned)((g.M + QBM - 1) / QBM);
-  if (g.N <= 32) {
+  if (narrow) {
     const dim3 grid(1, gm);
     if (bf) hipLaunchKernelGGL((gemm_bf16_kernel<32, true, QBK>), grid, dim3(256), 0, s, g);
     else hipLaunchKernelGGL((gemm_bf16_kernel<32, false, QBK>), grid, dim3(256), 0, s, g);
@@ -327,11 +328,49 @@ static void launch_tiled(const GemmB16Args& g, bool bf, hipStream_t s) {
   }
 }
 
+#ifndef MRL_GEMM_BF16_BK
+#define MRL_GEMM_BF16_BK 64
+#endif
+
+// The one decision of which NN kernel takes a product: mrl_gemm_bf16 launches what it
+// returns and mrl_gemm_bf16_route reports it.
+// lds_limit: the tiled kernel only (the big, streaming and small-M kernels hold 100-132 KB
+// of LDS per block, the first two for the whole product), with 32-deep K stages when the
+// 64-deep ones do not fit the limit; every NN kernel sums each output's k-steps of 16 in
+// the same order, so the results do not change
+static int nn_route(const GemmB16Args& g, bool dual, int64_t lds_limit, BigPlan* big, StreamPlan* st) {
+  const bool narrow = g.N <= 32;
+  const int t64 = narrow ? MRL_GEMM_ROUTE_TILED32_BK64 : MRL_GEMM_ROUTE_TILED128_BK64;
+  const int t32 = narrow ? MRL_GEMM_ROUTE_TILED32_BK32 : MRL_GEMM_ROUTE_TILED128_BK32;
+  if (lds_limit > 0)
+    return (int64_t)sizeof(bfr_t) * 2 * (QBM + (narrow ? 32 : 128)) * (64 + 8) <= lds_limit ? t64 : t32;
+  if (big_gemm_plan(g, dual, big)) return MRL_GEMM_ROUTE_BIG;  // tall products: 256 x 256
+  // small M (the Humanoid rollout's per-step layers): whole-K panels, 64 x 64 tiles
+  if (!dual && g.M <= env_or("MRL_GEMM_SMALL_MAX_M", MRL_GEMM_SMALL_MAX_M) && g.K <= 4 * SQK && g.N >= 64 &&
+      g.epi != MRL_GEMM_DTANH)
+    return MRL_GEMM_ROUTE_SMALL;
+  if (stream_gemm_plan(g, dual, st)) return st->kp == 384 ? MRL_GEMM_ROUTE_STREAM384 : MRL_GEMM_ROUTE_STREAM512;
+  return MRL_GEMM_BF16_BK == 64 ? t64 : t32;
+}
+
+static GemmB16Args nn_args(const mrl_gemm_bf16_desc* d, const int32_t* skip) {
+  return {d->m, d->n, d->k, d->a, d->bt, d->a2, d->bt2, d->lda, d->ldb,
+          d->c, d->ldc, d->bias, d->h, d->ldh, d->epilogue, skip};
+}
+
 }  // namespace mrl
 
 using namespace mrl;
 
 extern "C" {
+
+int32_t mrl_gemm_bf16_route(const mrl_gemm_bf16_desc* d) {
+  if (!d) return MRL_GEMM_ROUTE_INVALID;
+  if (d->m <= 0 || d->n <= 0) return MRL_GEMM_ROUTE_NONE;
+  BigPlan big;
+  StreamPlan st;
+  return nn_route(nn_args(d, nullptr), d->a2 != nullptr, d->lds_limit, &big, &st);
+}
 
 int mrl_gemm_bf16(const mrl_gemm_bf16_desc* d, const int32_t* skip, void* stream) {
   if (!d || !d->a || !d->bt || !d->c) return fail(E_ARG, "mrl_gemm_bf16: null pointer");
@@ -344,30 +383,25 @@ int mrl_gemm_bf16(const mrl_gemm_bf16_desc* d, const int32_t* skip, void* stream
                        reinterpret_cast<uintptr_t>(d->a2) | reinterpret_cast<uintptr_t>(d->bt2);
   if (al & 15) return fail(E_ARG, "mrl_gemm_bf16: operands must be 16-byte aligned");
   if (d->m <= 0 || d->n <= 0) return OK;
-  const GemmB16Args g = {d->m, d->n, d->k, d->a, d->bt, d->a2, d->bt2, d->lda, d->ldb,
-                         d->c, d->ldc, d->bias, d->h, d->ldh, d->epilogue, skip};
+  const GemmB16Args g = nn_args(d, skip);
   hipStream_t s = (hipStream_t)stream;
   const bool bf = d->c_bf16 != 0, dual = d->a2 != nullptr;
-#ifndef MRL_GEMM_BF16_BK
-#define MRL_GEMM_BF16_BK 64
-#endif
-  // lds_limit: the tiled kernel only (the big, streaming and small-M kernels hold 100-132 KB
-  // of LDS per block, the first two for the whole product), with 32-deep K stages when the
-  // 64-deep ones do not fit the limit; every NN kernel sums each output's k-steps of 16 in
-  // the same order, so the results do not change
-  if (d->lds_limit > 0) {
-    const bool k64 = (int64_t)sizeof(bfr_t) * 2 * (QBM + (g.N <= 32 ? 32 : 128)) * (64 + 8) <= d->lds_limit;
-    if (k64) launch_tiled<64>(g, bf, s);
-    else launch_tiled<32>(g, bf, s);
-  } else if (big_gemm_launch(g, bf, dual, s)) {  // tall products: the 256 x 256 kernel took it
-  } else if (!dual && g.M <= env_or("MRL_GEMM_SMALL_MAX_M", MRL_GEMM_SMALL_MAX_M) && g.K <= 4 * SQK && g.N >= 64 &&
-             g.epi != MRL_GEMM_DTANH) {
-    // small M (the Humanoid rollout's per-step layers): whole-K panels, 64 x 64 tiles
-    const dim3 grid((unsigned)((g.N + SBN - 1) / SBN), (unsigned)((g.M + SBM - 1) / SBM));
-    if (bf) hipLaunchKernelGGL((gemm_bf16_small_kernel<true>), grid, dim3(256), 0, s, g);
-    else hipLaunchKernelGGL((gemm_bf16_small_kernel<false>), grid, dim3(256), 0, s, g);
-  } else if (!stream_gemm_launch(g, bf, dual, s)) {
-    launch_tiled<MRL_GEMM_BF16_BK>(g, bf, s);
+  BigPlan big;
+  StreamPlan st;
+  switch (nn_route(g, dual, d->lds_limit, &big, &st)) {
+    case MRL_GEMM_ROUTE_BIG: big_gemm_launch(g, bf, dual, big, s); break;
+    case MRL_GEMM_ROUTE_SMALL: {
+      const dim3 grid((unsigned)((g.N + SBN - 1) / SBN), (unsigned)((g.M + SBM - 1) / SBM));
+      if (bf) hipLaunchKernelGGL((gemm_bf16_small_kernel<true>), grid, dim3(256), 0, s, g);
+      else hipLaunchKernelGGL((gemm_bf16_small_kernel<false>), grid, dim3(256), 0, s, g);
+      break;
+    }
+    case MRL_GEMM_ROUTE_STREAM384:
+    case MRL_GEMM_ROUTE_STREAM512: stream_gemm_launch(g, bf, st, s); break;
+    case MRL_GEMM_ROUTE_TILED128_BK64: launch_tiled<64>(g, false, bf, s); break;
+    case MRL_GEMM_ROUTE_TILED32_BK64: launch_tiled<64>(g, true, bf, s); break;
+    case MRL_GEMM_ROUTE_TILED128_BK32: launch_tiled<32>(g, false, bf, s); break;
+    default: launch_tiled<32>(g, true, bf, s); break;
   }
   return hip_check(hipGetLastError(), "mrl_gemm_bf16");
 }

@@ -27,12 +27,6 @@ namespace mrl {
 constexpr int BBM = 256, BBN = 256, BBK = 32;
 constexpr int BSTAGE = (BBM + BBN) * BBK;  // bf16 per stage: A rows, then Bt rows (16 K each)
 
-struct BigPlan {
-  int64_t ntm;  // row tiles
-  int ntn;      // column tiles
-  int per_xcd;  // blocks per XCD
-};
-
 // DT: the DTANH epilogue (H operand), compiled apart so the others carry no H registers
 template <bool DUAL, bool OUTBF, bool DT>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_big_kernel(GemmB16Args g, BigPlan pl) {
@@ -288,17 +282,20 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_big_kernel(GemmB16Args g, Bi
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no DMA outlives the block
 }
 
-bool big_gemm_launch(const GemmB16Args& g, bool outbf, bool dual, hipStream_t s) {
+bool big_gemm_plan(const GemmB16Args& g, bool dual, BigPlan* pl) {
   const int64_t min_m = env_or("MRL_GEMM_BIG_MIN_M", MRL_GEMM_BIG_MIN_M);
   const int64_t ntk = (g.K + BBK - 1) / BBK, nst = (dual ? 2 : 1) * ntk;
-  if (min_m <= 0 || g.M < min_m || g.N < 128 || nst % 4 != 0) return false;
+  // nst = 0 (K = 0) is no stage stream at all: the tiled kernel's guarded loop takes it
+  if (min_m <= 0 || g.M < min_m || g.N < 128 || nst <= 0 || nst % 4 != 0) return false;
   const int ncu = cu_count();
   if (ncu == 0) return false;
-  BigPlan pl;
-  pl.ntm = (g.M + BBM - 1) / BBM;
-  pl.ntn = (int)((g.N + BBN - 1) / BBN);
-  pl.per_xcd = (ncu / 8) / pl.ntn * pl.ntn;  // whole groups of the ntn column tiles
-  if (pl.per_xcd < pl.ntn) return false;
+  pl->ntm = (g.M + BBM - 1) / BBM;
+  pl->ntn = (int)((g.N + BBN - 1) / BBN);
+  pl->per_xcd = (ncu / 8) / pl->ntn * pl->ntn;  // whole groups of the ntn column tiles
+  return pl->per_xcd >= pl->ntn;
+}
+
+void big_gemm_launch(const GemmB16Args& g, bool outbf, bool dual, const BigPlan& pl, hipStream_t s) {
   const dim3 grid((unsigned)(8 * pl.per_xcd)), blk(512);
 #define MRL_BIG(DU, OB)                                                                       \
   do {                                                                                        \
@@ -308,7 +305,6 @@ bool big_gemm_launch(const GemmB16Args& g, bool outbf, bool dual, hipStream_t s)
   if (dual) { if (outbf) MRL_BIG(true, true); else MRL_BIG(true, false); }
   else { if (outbf) MRL_BIG(false, true); else MRL_BIG(false, false); }
 #undef MRL_BIG
-  return true;
 }
 
 }  // namespace mrl

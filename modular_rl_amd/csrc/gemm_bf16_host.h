@@ -36,11 +36,29 @@ inline int cu_count() {
 
 struct GemmB16Args;
 
-// The 256 x 256 kernel for a tall NN product (a multiple of four 32-deep K stages, N >= 128,
-// one 512-thread block per CU): launched here and true, or false.  gemm_bf16_big.hip
-bool big_gemm_launch(const GemmB16Args& g, bool outbf, bool dual, hipStream_t s);
-// The streaming kernel for a tall NN product (K of 257..512, N >= 64, one block per CU):
-// launched here and true, or false (the tiled kernel runs).  gemm_bf16_stream.hip
-bool stream_gemm_launch(const GemmB16Args& g, bool outbf, bool dual, hipStream_t s);
+// Each persistent kernel's decision is one `plan` function, which both mrl_gemm_bf16 and
+// mrl_gemm_bf16_route go through (gemm_bf16.hip's nn_route); the `launch` functions only
+// launch what a plan accepted.
+struct BigPlan {
+  int64_t ntm;  // row tiles
+  int ntn;      // column tiles
+  int per_xcd;  // blocks per XCD
+};
+struct StreamPlan {
+  int nslice, groups_per_xcd;
+  int kp;   // K plan: 384 or 512
+  int ncu;  // blocks launched (those past 8 groups_per_xcd nslice return at once)
+};
+
+// The 256 x 256 kernel for a tall NN product (a positive multiple of four 32-deep K stages,
+// N >= 128, one 512-thread block per CU): whether it takes the product, and its plan.
+// gemm_bf16_big.hip
+bool big_gemm_plan(const GemmB16Args& g, bool dual, BigPlan* pl);
+void big_gemm_launch(const GemmB16Args& g, bool outbf, bool dual, const BigPlan& pl, hipStream_t s);
+// The streaming kernel for a tall single NN product (K of 257..512 with rows that cover all
+// but the plan's last k-step, N >= 64, one block per CU): whether it takes the product (else
+// the tiled kernel runs), and its plan.  gemm_bf16_stream.hip
+bool stream_gemm_plan(const GemmB16Args& g, bool dual, StreamPlan* pl);
+void stream_gemm_launch(const GemmB16Args& g, bool outbf, const StreamPlan& pl, hipStream_t s);
 
 }  // namespace mrl

@@ -22,10 +22,6 @@
 
 namespace mrl {
 
-struct StreamPlan {
-  int nslice, groups_per_xcd;
-};
-
 template <int KP, bool DUAL, bool OUTBF>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_stream_kernel(GemmB16Args g, StreamPlan pl) {
   constexpr int BN = DUAL ? 64 : 128;  // output columns per block
@@ -162,27 +158,33 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_stream_kernel(GemmB16Args g,
   }
 }
 
-bool stream_gemm_launch(const GemmB16Args& g, bool outbf, bool dual, hipStream_t s) {
+bool stream_gemm_plan(const GemmB16Args& g, bool dual, StreamPlan* pl) {
   const int64_t min_m = env_or("MRL_GEMM_STREAM_MIN_M", MRL_GEMM_STREAM_MIN_M);
   // the dual product (JVP: A.B + A2.B2) measured slower streamed (2.72 vs 1.93 ms at
   // M = 1 M, K = N = 512: twice the A traffic per MFMA through one BN = 64 slice) -> tiled
   if (min_m <= 0 || dual || g.M < min_m || g.N < 64 || g.K <= 256 || g.K > 512) return false;
+  // the kernel's A loads bound only the plan's last k-step by lda (every other one reads
+  // 16 k unmasked), so a row must reach that step: K <= 367 on the 384 plan and 385..495
+  // on the 512 plan with lda = K rounded up to 8 would read past the row -> tiled
+  pl->kp = g.K <= 384 ? 384 : 512;
+  if (g.lda < pl->kp - 16) return false;
   const int ncu = cu_count();
   if (ncu == 0) return false;
-  const int bn = dual ? 64 : 128;
-  StreamPlan pl;
-  pl.nslice = (int)((g.N + bn - 1) / bn);
-  pl.groups_per_xcd = (ncu / 8) / pl.nslice;
-  if (pl.groups_per_xcd < 1) return false;
-  const dim3 grid((unsigned)ncu), blk(512);
+  pl->ncu = ncu;
+  pl->nslice = (int)((g.N + 127) / 128);
+  pl->groups_per_xcd = (ncu / 8) / pl->nslice;
+  return pl->groups_per_xcd >= 1;
+}
+
+void stream_gemm_launch(const GemmB16Args& g, bool outbf, const StreamPlan& pl, hipStream_t s) {
+  const dim3 grid((unsigned)pl.ncu), blk(512);
 #define MRL_STREAM(KP, DU, OB) hipLaunchKernelGGL((gemm_bf16_stream_kernel<KP, DU, OB>), grid, blk, 0, s, g, pl)
-  if (g.K <= 384) {
+  if (pl.kp == 384) {
     if (outbf) MRL_STREAM(384, false, true); else MRL_STREAM(384, false, false);
   } else {
     if (outbf) MRL_STREAM(512, false, true); else MRL_STREAM(512, false, false);
   }
 #undef MRL_STREAM
-  return true;
 }
 
 }  // namespace mrl

@@ -322,9 +322,32 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_tn_big_kernel(GemmTnArgs g, 
   }
 }
 
+// The one decision of mrl_gemm_bf16_tn: the split (gemm.hip's slab GEMMs: mrl_gemm_slab_splits
+// slabs of whole 32-row steps) and which kernel takes it.  256 x 256 tiles for the wide
+// layers (m_real, N >= 256, multiples of 8; the ones-row rides row tile 0); lds_limit: the
+// 41 KB tiled kernel.  mrl_gemm_bf16_tn launches what it returns, mrl_gemm_bf16_tn_route
+// reports it.
+static int tn_route(const mrl_gemm_bf16_tn_desc* d, int64_t* k_chunk, int64_t* z) {
+  const int64_t m_real = d->m - (d->ones_row ? 1 : 0);
+  const int64_t req = d->splits < 1 ? 1 : d->splits;
+  *k_chunk = ((d->k + req - 1) / req + TBK - 1) / TBK * TBK;
+  if (*k_chunk < TBK) *k_chunk = TBK;
+  *z = d->k > 0 ? (d->k + *k_chunk - 1) / *k_chunk : 1;
+  const bool big = env_or("MRL_GEMM_TN_BIG", 1) != 0 && d->lds_limit <= 0;
+  if (big && m_real >= TBM && d->n >= TBN && m_real % 8 == 0 && d->n % 8 == 0) return MRL_GEMM_ROUTE_TN_BIG;
+  return d->n <= 32 ? MRL_GEMM_ROUTE_TN_TILED32 : MRL_GEMM_ROUTE_TN_TILED128;
+}
+
 }  // namespace mrl
 
 using namespace mrl;
+
+extern "C" int32_t mrl_gemm_bf16_tn_route(const mrl_gemm_bf16_tn_desc* d) {
+  if (!d) return MRL_GEMM_ROUTE_INVALID;
+  if (d->m <= 0 || d->n <= 0) return MRL_GEMM_ROUTE_NONE;
+  int64_t k_chunk, z;
+  return tn_route(d, &k_chunk, &z);
+}
 
 extern "C" int mrl_gemm_bf16_tn(const mrl_gemm_bf16_tn_desc* d, const int32_t* skip, void* stream) {
   if (!d || !d->a || !d->b || !d->slab) return fail(E_ARG, "mrl_gemm_bf16_tn: null pointer");
@@ -334,18 +357,13 @@ extern "C" int mrl_gemm_bf16_tn(const mrl_gemm_bf16_tn_desc* d, const int32_t* s
   if ((reinterpret_cast<uintptr_t>(d->a) | reinterpret_cast<uintptr_t>(d->b)) & 15)
     return fail(E_ARG, "mrl_gemm_bf16_tn: operands must be 16-byte aligned");
   if (d->m <= 0 || d->n <= 0) return OK;
-  // the split of gemm.hip's slab GEMMs (mrl_gemm_slab_splits slabs of whole 32-row steps)
-  const int64_t req = d->splits < 1 ? 1 : d->splits;
-  int64_t k_chunk = ((d->k + req - 1) / req + TBK - 1) / TBK * TBK;
-  if (k_chunk < TBK) k_chunk = TBK;
-  const int64_t z = d->k > 0 ? (d->k + k_chunk - 1) / k_chunk : 1;
+  int64_t k_chunk, z;
+  const int route = tn_route(d, &k_chunk, &z);
   if (z > 65535) return fail(E_ARG, "mrl_gemm_bf16_tn: too many splits");
   const GemmTnArgs g = {d->m, d->n, d->k, d->a, d->b, d->lda, d->ldb, m_real, k_chunk, d->slab, d->slab_stride, d->ldc, skip};
   hipStream_t s = (hipStream_t)stream;
-  // 256 x 256 tiles for the wide layers (m_real, N >= 256; the ones-row rides row tile 0);
-  // lds_limit: the 41 KB tiled kernel
-  const bool big = env_or("MRL_GEMM_TN_BIG", 1) != 0 && d->lds_limit <= 0;
-  if (big && g.m_real >= TBM && g.N >= TBN && g.m_real % 8 == 0 && g.N % 8 == 0) {
+  const unsigned gm = (unsigned)((g.M + QBM - 1) / QBM);
+  if (route == MRL_GEMM_ROUTE_TN_BIG) {
     TnPlan pl;
     pl.ntm = (int)((g.m_real + TBM - 1) / TBM);
     pl.ntn = (int)((g.N + TBN - 1) / TBN);
@@ -356,11 +374,11 @@ extern "C" int mrl_gemm_bf16_tn(const mrl_gemm_bf16_tn_desc* d, const int32_t* s
       hipLaunchKernelGGL(gemm_bf16_tn_big_kernel<true>, dim3((unsigned)(8 * rounds * ntile)), dim3(512), 0, s, g, pl);
     else
       hipLaunchKernelGGL(gemm_bf16_tn_big_kernel<false>, dim3((unsigned)(8 * rounds * ntile)), dim3(512), 0, s, g, pl);
-    return hip_check(hipGetLastError(), "mrl_gemm_bf16_tn");
+  } else if (route == MRL_GEMM_ROUTE_TN_TILED32) {
+    hipLaunchKernelGGL((gemm_bf16_tn_kernel<32>), dim3(1, gm, (unsigned)z), dim3(256), 0, s, g);
+  } else {
+    hipLaunchKernelGGL((gemm_bf16_tn_kernel<128>), dim3((unsigned)((g.N + 127) / 128), gm, (unsigned)z), dim3(256), 0,
+                       s, g);
   }
-  const unsigned gm = (unsigned)((g.M + QBM - 1) / QBM);
-  if (g.N <= 32) hipLaunchKernelGGL((gemm_bf16_tn_kernel<32>), dim3(1, gm, (unsigned)z), dim3(256), 0, s, g);
-  else hipLaunchKernelGGL((gemm_bf16_tn_kernel<128>), dim3((unsigned)((g.N + 127) / 128), gm, (unsigned)z), dim3(256), 0,
-                          s, g);
   return hip_check(hipGetLastError(), "mrl_gemm_bf16_tn");
 }

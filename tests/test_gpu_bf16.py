@@ -894,9 +894,10 @@ def test_bf16_gemm_epilogue_tails(monkeypatch):
     tiles and a partial column tile per kernel.  (a) every kernel equals the tiled one bit
     for bit on the M x N block; (b) the tiled result is within 2e-5 (f32) / 8e-3 (bf16
     output) of the float64 product of the bf16 operands; (c) the padding columns
-    N <= c < ldc keep their sentinel.  The streaming shapes' A and Bt carry lda = ldb =
-    the kernel's K plan (384 / 512): its A fragments of all but the last k-step are read
-    without a bound, so a row shorter than the plan less 16 is read past its end."""
+    N <= c < ldc keep their sentinel.  The streaming shapes carry lda = ldb = the kernel's
+    K plan (384 / 512) and lda = ldb = K rounded up to 8, the layered path's form: 376 and
+    504 stream with their last k-step masked, 264 is a row too short for the plan, which
+    the launcher hands to the tiled kernel."""
     import ctypes
 
     from modular_rl_amd import _lib
@@ -910,6 +911,9 @@ def test_bf16_gemm_epilogue_tails(monkeypatch):
                                             ("small", ("0", "0", "8192"), 70, 70, 40, 40, False),
                                             ("stream", ("0", "1", "0"), 300, 70, 264, 384, True),
                                             ("stream", ("0", "1", "0"), 300, 70, 392, 512, True),
+                                            ("stream", ("0", "1", "0"), 300, 70, 376, 376, True),
+                                            ("stream", ("0", "1", "0"), 300, 70, 504, 504, True),
+                                            ("stream", ("0", "1", "0"), 300, 70, 264, 264, True),
                                             ("big", ("1", "0", None), 300, 140, 128, 128, True)]:
         A, W = rng.standard_normal((M, K)), rng.standard_normal((K, N)) * 0.05
         bias = rng.standard_normal(N).astype(np.float32)
