@@ -232,6 +232,20 @@ __device__ inline void load_noise(const RollArgs& a, int64_t row, double* zn) {
     for (int q = 0; q < EC::ACT; ++q) zn[q] = nz[row * EC::ACT + q];
 }
 
+// z + sd * noise in fp32 with the product rounded before the sum (core.py:432-435: numpy's two
+// roundings).  __fmul_rn / __fadd_rn do not give that: the compiler's headers define them as
+// plain * and +, which the default -ffp-contract fuses into one v_fma_f32 (one rounding), so
+// the contraction is switched off for this product and sum.  The layered rollout's kernels
+// sample with it (tests/test_gpu_layered_step.py holds their actions to the two roundings bit
+// for bit); the fused 64-64 step kernels (QUAD) keep the contracted form they have always
+// computed -- at most one ulp of the action away -- because their trajectories are what the fused
+// rollout tests and the benchmark were recorded against
+__device__ inline float mul_then_add(float a, float b, float c) {
+#pragma clang fp contract(off)
+  const float p = a * b;
+  return p + c;
+}
+
 // sample the action from the head rows z (core.py:261-267; distributions.py:3-13 /
 // core.py:432-435), write act/prob rows, step the env (fp64)
 // QUAD: the four 16-lane rows of the wave hold this env (fused step kernel); every
@@ -279,7 +293,7 @@ __device__ inline void sample_and_step(const RollArgs& a, int64_t row, const flo
 #pragma unroll
     for (int q = 0; q < A; ++q) {
       const float sd = SD ? logstd[q] : expf(logstd[q]);
-      av[q] = __fadd_rn(__fmul_rn((float)zn[q], sd), z[q]);
+      av[q] = QUAD ? __fadd_rn(__fmul_rn((float)zn[q], sd), z[q]) : mul_then_add((float)zn[q], sd, z[q]);
       if (store) {
         reinterpret_cast<float*>(a.b.act)[row * A + q] = av[q];
         a.b.prob[row * 2 * A + q] = z[q];

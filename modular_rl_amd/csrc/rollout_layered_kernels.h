@@ -305,7 +305,7 @@ __global__ __launch_bounds__(64 * WPB) void hm_act_kernel(RollArgs a, const floa
     float av = z;  // EV: the mean, no noise row is read
     if constexpr (!EV) {
       const double zn = reinterpret_cast<const double*>(a.b.noise)[row * A + lane];
-      av = __fadd_rn(__fmul_rn((float)zn, sd), z);
+      av = mul_then_add((float)zn, sd, z);
     }
     reinterpret_cast<float*>(a.b.act)[row * A + lane] = av;
     a.b.prob[row * 2 * A + lane] = z;
