@@ -74,6 +74,13 @@ int mrl_mlp_pack(const mrl_mlp_desc* d, const float* theta, float* image, int32_
 #define MRL_EPI_PPOSGD 6    /* one launch = one minibatch of n <= MRL_PPO_BLOCK_ROWS rows: block-reduced
                                kl, c = kl_coeff + 2 cutoff_coeff (kl - cutoff)+, ghead of pensurr
                                (ppo.py:150-156); partial sums as LOSSES                            */
+/* 7 is not an epilogue (MRL_E_ARG "unknown epilogue") */
+#define MRL_EPI_PPOCLIP 8   /* the clipped surrogate, eps = kl_cutoff in (0, 1): partial <- (sum min(r adv,
+                               clamp(r, 1 - eps, 1 + eps) adv), sum KL(old,new), sum ent), r = the
+                               LOSSES ratio, the bounds 1 -+ eps formed in float; ghead <- SURRGRAD's
+                               rows, all zero for a clipped row ((adv > 0 and r > 1 + eps) or (adv < 0
+                               and r < 1 - eps), strict).  A plain per-row forward epilogue: any n,
+                               the full row grid, MRL_CACHE_WRITE allowed; reverse_kl is not read  */
 #define MRL_PPO_BLOCK_ROWS 128
 
 typedef struct {
@@ -93,7 +100,7 @@ typedef struct {
   float* ghead;            /* [N, gh] head-gradient rows (gh = k, 2d or 1)         */
   double* partial;         /* [mrl_partial_rows(n), 4] fp64 per-wave partial sums  */
   double kl_coeff;         /* PPO epilogues (see MRL_EPI_PPOGRAD / PPOSGD)         */
-  double kl_cutoff;        /* PPOSGD: 2 * kl_target                                */
+  double kl_cutoff;        /* PPOSGD: 2 * kl_target; PPOCLIP: the clip range       */
   double cutoff_coeff;     /* PPOSGD: kl_cutoff_coeff (1000)                       */
   int32_t reverse_kl;      /* kl[new, old] instead of kl[old, new] (PpoLbfgs)     */
   int32_t cache_mode;      /* MRL_CACHE_* (fused path; act_cache NULL = no cache) */
@@ -107,7 +114,7 @@ typedef struct {
 /* Primal activation cache of the fused path: the forward of one theta is shared by
  * every Fisher product of an update (trpo.py:70 is called 10-11 times at a fixed
  * theta) and by the VJP that follows a loss pass.  A plain-forward epilogue (PROB,
- * LOSSES, SURRGRAD, VFLOSS, PPOGRAD) with MRL_CACHE_WRITE stores h1/h2; EPI_FVP with
+ * LOSSES, SURRGRAD, VFLOSS, PPOGRAD, PPOCLIP) with MRL_CACHE_WRITE stores h1/h2; EPI_FVP with
  * MRL_CACHE_READ and mrl_mlp_vjp with a non-NULL cache read them instead of
  * recomputing the forward (bitwise the same activations). */
 #define MRL_CACHE_NONE 0

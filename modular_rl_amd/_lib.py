@@ -17,6 +17,7 @@ OK = 0
 HEAD_LINEAR, HEAD_SOFTMAX, HEAD_GAUSS = 0, 1, 2
 CACHE_NONE, CACHE_WRITE, CACHE_READ = 0, 1, 2
 EPI_PROB, EPI_LOSSES, EPI_SURRGRAD, EPI_VFLOSS, EPI_FVP, EPI_PPOGRAD, EPI_PPOSGD = 0, 1, 2, 3, 4, 5, 6
+EPI_PPOCLIP = 8  # the clipped surrogate; the clip range travels in RowsIO.kl_cutoff (7 is not an epilogue)
 PPO_BLOCK_ROWS = 128
 ENV_CARTPOLE, ENV_HOPPER, ENV_HUMANOID = 0, 1, 2
 ENV_PENDULUM, ENV_MOUNTAINCAR, ENV_ACROBOT = 4, 5, 6  # 3 is not an env

@@ -18,7 +18,7 @@ from .envs import Box, Discrete
 from .filters import DeviceZFilter
 from .misc_utils import IDENTITY, comma_sep_ints, update_default_config
 from .nets import check_hid_sizes, glorot_init, make_net
-from .ppo import PpoLbfgsUpdater, PpoSgdUpdater
+from .ppo import PpoClipUpdater, PpoLbfgsUpdater, PpoSgdUpdater
 from .trpo import TrpoUpdater
 from .vf import NnVf
 
@@ -169,6 +169,13 @@ class PpoSgdAgent(TrpoAgent):
     """`agentzoo.py:143-150`: PPO with minibatch Adam."""
     options = MLP_OPTIONS + PG_OPTIONS + PpoSgdUpdater.options + FILTER_OPTIONS
     updater_cls = PpoSgdUpdater
+
+
+class PpoClipAgent(TrpoAgent):
+    """PPO with the clipped surrogate and multi-epoch minibatch Adam (``ppo.PpoClipUpdater``;
+    not in the reference's zoo)."""
+    options = MLP_OPTIONS + PG_OPTIONS + PpoClipUpdater.options + FILTER_OPTIONS
+    updater_cls = PpoClipUpdater
 
 
 class FrozenZFilter:

@@ -465,6 +465,7 @@ static void launch_head(int epi, dim3 grid, hipStream_t s, const RowsArgs& a, co
     case MRL_EPI_SURRGRAD: hipLaunchKernelGGL((head_rows_kernel<MRL_EPI_SURRGRAD, MA>), grid, dim3(256), 0, s, a, z, dz, skip); break;
     case MRL_EPI_VFLOSS: hipLaunchKernelGGL((head_rows_kernel<MRL_EPI_VFLOSS, MA>), grid, dim3(256), 0, s, a, z, dz, skip); break;
     case MRL_EPI_PPOGRAD: hipLaunchKernelGGL((head_rows_kernel<MRL_EPI_PPOGRAD, MA>), grid, dim3(256), 0, s, a, z, dz, skip); break;
+    case MRL_EPI_PPOCLIP: hipLaunchKernelGGL((head_rows_kernel<MRL_EPI_PPOCLIP, MA>), grid, dim3(256), 0, s, a, z, dz, skip); break;
     case MRL_EPI_PPOSGD: hipLaunchKernelGGL((head_rows_kernel<MRL_EPI_PPOSGD, MA>), dim3(1), dim3(256), 0, s, a, z, dz, skip); break;
     default: hipLaunchKernelGGL((head_rows_kernel<MRL_EPI_FVP, MA>), grid, dim3(256), 0, s, a, z, dz, skip); break;
   }
@@ -589,10 +590,12 @@ int mrl_head_rows(int32_t head, int32_t n_out, int32_t epi, const float* z, cons
     case MRL_EPI_SURRGRAD:
     case MRL_EPI_PPOGRAD:
     case MRL_EPI_PPOSGD:
+    case MRL_EPI_PPOCLIP:
       if (head == MRL_HEAD_LINEAR) return fail(E_ARG, "policy epilogue on a value net");
       if (!io->act || !io->adv || !io->oldprob || !io->partial) return fail(E_ARG, "losses need act/adv/oldprob/partial");
       if (epi != MRL_EPI_LOSSES && !io->ghead) return fail(E_ARG, "gradient epilogues need ghead");
       if (epi == MRL_EPI_PPOSGD && io->n > MRL_PPO_BLOCK_ROWS) return fail(E_ARG, "PPOSGD minibatch exceeds one block");
+      if (epi == MRL_EPI_PPOCLIP && !clip_range_ok(io->kl_cutoff)) return fail(E_ARG, "PPOCLIP needs a clip range in (0, 1)");
       break;
     case MRL_EPI_VFLOSS:
       if (head != MRL_HEAD_LINEAR || !io->target || !io->ghead || !io->partial)
@@ -624,7 +627,7 @@ int mrl_head_rows(int32_t head, int32_t n_out, int32_t epi, const float* z, cons
   a.kl_coeff = (float)io->kl_coeff;
   a.kl_cutoff = (float)io->kl_cutoff;
   a.cutoff_coeff = (float)io->cutoff_coeff;
-  a.reverse_kl = io->reverse_kl;
+  a.reverse_kl = epi == MRL_EPI_PPOCLIP ? 0 : io->reverse_kl;
   const dim3 grid((unsigned)(mrl_partial_rows(io->n) / 4));
   if (n_out <= 8) launch_head<8>(epi, grid, (hipStream_t)stream, a, z, dz, skip);
   else launch_head<MRL_LAYERED_MAX_OUT>(epi, grid, (hipStream_t)stream, a, z, dz, skip);

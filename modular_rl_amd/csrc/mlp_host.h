@@ -119,6 +119,7 @@ inline void with_rows_epilogue(int epi, int cache_mode, F&& f) {
       return f(std::integral_constant<int, MRL_EPI_FVP>{});
     case MRL_EPI_PPOGRAD: return f(std::integral_constant<int, MRL_EPI_PPOGRAD>{});
     case MRL_EPI_PPOSGD: return f(std::integral_constant<int, MRL_EPI_PPOSGD>{});
+    case MRL_EPI_PPOCLIP: return f(std::integral_constant<int, MRL_EPI_PPOCLIP>{});
   }
 }
 
@@ -174,7 +175,7 @@ inline int rows_args(const mrl_mlp_desc* d, int32_t epi, const float* theta, con
   a.kl_coeff = (float)io->kl_coeff;
   a.kl_cutoff = (float)io->kl_cutoff;
   a.cutoff_coeff = (float)io->cutoff_coeff;
-  a.reverse_kl = io->reverse_kl;
+  a.reverse_kl = epi == MRL_EPI_PPOCLIP ? 0 : io->reverse_kl;
   a.feat = io->feat_out;
   if (a.feat != nullptr && (epi != MRL_EPI_PROB || io->ep_t == nullptr))
     return fail(E_ARG, "feat_out is for MRL_EPI_PROB with ep_t (the value prediction)");
@@ -190,11 +191,13 @@ inline int rows_args(const mrl_mlp_desc* d, int32_t epi, const float* theta, con
     case MRL_EPI_SURRGRAD:
     case MRL_EPI_PPOGRAD:
     case MRL_EPI_PPOSGD:
+    case MRL_EPI_PPOCLIP:
       if (d->head == MRL_HEAD_LINEAR) return fail(E_ARG, "policy epilogue on a value net");
       if (!io->act || !io->adv || !io->oldprob || !io->partial) return fail(E_ARG, "losses need act/adv/oldprob/partial");
       if (epi != MRL_EPI_LOSSES && !io->ghead) return fail(E_ARG, "gradient epilogues need ghead");
       if (d->head == MRL_HEAD_GAUSS && !theta) return fail(E_ARG, "DiagGauss needs theta (logstd)");
       if (epi == MRL_EPI_PPOSGD && io->n > MRL_PPO_BLOCK_ROWS) return fail(E_ARG, "PPOSGD minibatch exceeds one block");
+      if (epi == MRL_EPI_PPOCLIP && !clip_range_ok(io->kl_cutoff)) return fail(E_ARG, "PPOCLIP needs a clip range in (0, 1)");
       break;
     case MRL_EPI_VFLOSS:
       if (d->head != MRL_HEAD_LINEAR || !io->target || !io->ghead || !io->partial)

@@ -29,12 +29,16 @@ struct RowsArgs {
   const float* dlogstd;  // tangent + tls (EPI_FVP, DiagGauss) or nullptr
   // PPO (ppo.py:3-229): pensurr = surr + c_kl * kl + cutoff_coeff * (kl > cutoff) (kl - cutoff)^2
   float kl_coeff;        // EPI_PPOGRAD: the full d pensurr / d kl (host-computed); EPI_PPOSGD: kl_coeff
-  float kl_cutoff, cutoff_coeff;
+  float kl_cutoff, cutoff_coeff;  // EPI_PPOCLIP: kl_cutoff is the clip range
   int reverse_kl;        // kl[new, old] instead of kl[old, new]
   float* cache;          // primal activation cache (fused path) or nullptr
   int cache_mode;        // MRL_CACHE_WRITE: the forward stores h1/h2; MRL_CACHE_READ: FVP reads them
   float* feat;           // EPI_PROB with ep_t: the input rows [obs, t / limit] written beside the values
 };
+
+// EPI_PPOCLIP's clip range (mrl_rows_io.kl_cutoff), checked on the host: finite and inside
+// (0, 1) -- a NaN fails both comparisons
+inline bool clip_range_ok(double eps) { return eps > 0.0 && eps < 1.0; }
 
 constexpr int EPI_FVP_CACHED = 100;  // internal: MRL_EPI_FVP reading the activation cache
 
@@ -114,6 +118,17 @@ __device__ __forceinline__ void fvp_metric_row(const RowsArgs& a, const float (&
   }
 }
 
+// EPI_PPOCLIP (the clipped surrogate min(r A, clamp(r, 1 - eps, 1 + eps) A), eps = kl_cutoff):
+// the row's surrogate term, and whether the row is clipped -- the minimum is the constant
+// clamp bound times A, so the row has no gradient: (A > 0 and r > 1 + eps) or (A < 0 and
+// r < 1 - eps), strict, a row on the bound keeps its gradient.  An unclipped row's term is
+// r A itself (either clamp(r) == r or r A is the smaller product).
+__device__ __forceinline__ float ppoclip_term(float eps, float ratio, float advr, bool& clipped) {
+  const float lo = 1.f - eps, hi = 1.f + eps;
+  clipped = (advr > 0.f && ratio > hi) || (advr < 0.f && ratio < lo);
+  return fminf(ratio * advr, fminf(fmaxf(ratio, lo), hi) * advr);
+}
+
 // a head-gradient store.  LDS destinations (the one-pass policy gradient's mailbox,
 // mlp_fisher_hyb_kernel PROD 1) take the value through an identity DPP move first: an LDS
 // op must not read a packed-f32 VALU result within 8 wait states (mlp_device.h; hipcc
@@ -145,9 +160,10 @@ __device__ __forceinline__ void row_epilogue(const RowsArgs& a, int64_t row, con
         a.out[row * 2 * A + A + j] = sd[j];
       }
     }
-  } else if (EPI == MRL_EPI_LOSSES || EPI == MRL_EPI_SURRGRAD || EPI == MRL_EPI_PPOGRAD) {
+  } else if (EPI == MRL_EPI_LOSSES || EPI == MRL_EPI_SURRGRAD || EPI == MRL_EPI_PPOGRAD || EPI == MRL_EPI_PPOCLIP) {
     // surrogate term ratio*adv, KL and entropy of the row; SURRGRAD / PPOGRAD also write
-    // the head gradient of surr (+ kl_coeff * kl for PPO)
+    // the head gradient of surr (+ kl_coeff * kl for PPO).  PPOCLIP: SURRGRAD with the
+    // clipped surrogate term and a zero weight w for a clipped row
     const float advr = a.adv[row];
     const float c = a.kl_coeff * (float)a.inv_ng;
     if (a.head == MRL_HEAD_SOFTMAX) {
@@ -166,11 +182,13 @@ __device__ __forceinline__ void row_epilogue(const RowsArgs& a, int64_t row, con
         ent += cat_ent_term(p[j]);
       }
       const float ratio = expf(logf(pa) - logf(opa));
-      acc0 += (double)(ratio * advr);
+      bool clipped = false;
+      if (EPI == MRL_EPI_PPOCLIP) acc0 += (double)ppoclip_term(a.kl_cutoff, ratio, advr, clipped);
+      else acc0 += (double)(ratio * advr);
       acc1 += (double)kl;
       acc2 += (double)ent;
-      if (EPI == MRL_EPI_SURRGRAD || EPI == MRL_EPI_PPOGRAD) {
-        const float w = (float)(-a.inv_ng) * ratio * advr;
+      if (EPI == MRL_EPI_SURRGRAD || EPI == MRL_EPI_PPOGRAD || EPI == MRL_EPI_PPOCLIP) {
+        const float w = clipped ? 0.f : (float)(-a.inv_ng) * ratio * advr;
         for (int j = 0; j < A; ++j) {
           float gj = w * ((j == act ? 1.f : 0.f) - p[j]);
           if (EPI == MRL_EPI_PPOGRAD)
@@ -197,11 +215,13 @@ __device__ __forceinline__ void row_epilogue(const RowsArgs& a, int64_t row, con
       const float logp = gauss_loglik(q, sls, A);
       const float oldlogp = gauss_loglik(q0, sls0, A);
       const float ratio = expf(logp - oldlogp);
-      acc0 += (double)(ratio * advr);
+      bool clipped = false;
+      if (EPI == MRL_EPI_PPOCLIP) acc0 += (double)ppoclip_term(a.kl_cutoff, ratio, advr, clipped);
+      else acc0 += (double)(ratio * advr);
       acc1 += (double)kl;
       acc2 += (double)gauss_entropy(sls, A);
-      if (EPI == MRL_EPI_SURRGRAD || EPI == MRL_EPI_PPOGRAD) {
-        const float w = (float)(-a.inv_ng) * ratio * advr;
+      if (EPI == MRL_EPI_SURRGRAD || EPI == MRL_EPI_PPOGRAD || EPI == MRL_EPI_PPOCLIP) {
+        const float w = clipped ? 0.f : (float)(-a.inv_ng) * ratio * advr;
         for (int j = 0; j < A; ++j) {
           float gm = w * u[j] / sd[j];
           float gs = w * (u[j] * u[j] - 1.f);

@@ -104,6 +104,15 @@ class Workspace:
         return t[:numel]
 
 
+def _clip_range(epi, clip, kl_cutoff):
+    """rows(..., clip=eps): EPI_PPOCLIP's clip range, which the C ABI takes in RowsIO.kl_cutoff."""
+    if clip is None:
+        return kl_cutoff
+    if epi != _lib.EPI_PPOCLIP:
+        raise MrlError("clip is EPI_PPOCLIP's clip range")
+    return clip
+
+
 _SPLIT_ROWS_EPIS = (_lib.EPI_PROB, _lib.EPI_LOSSES, _lib.EPI_SURRGRAD, _lib.EPI_VFLOSS)
 
 
@@ -209,15 +218,16 @@ class MlpNet:
     # ---- fused passes
     def rows(self, epi, x, n, ep_t=None, timestep_limit=1.0, inv_n_global=1.0, act=None, adv=None, oldprob=None,
              target=None, out=None, ghead=None, partial=None, theta=None, image=None, tangent=None, image_t=None,
-             skip=None, kl_coeff=0.0, kl_cutoff=0.0, cutoff_coeff=0.0, reverse_kl=0, feat_out=None):
+             skip=None, kl_coeff=0.0, kl_cutoff=0.0, cutoff_coeff=0.0, reverse_kl=0, feat_out=None, clip=None):
         self._check_time_feature(ep_t)
+        kl_cutoff = _clip_range(epi, clip, kl_cutoff)
         own = (theta is None or theta is self.theta) and (image is None or image is self.image)
         theta = self.theta if theta is None else theta
         image = self.image if image is None else image
         mode, cache = _lib.CACHE_NONE, None
         if self.use_cache and own:
             key = self._key(x, n, ep_t, timestep_limit)
-            if epi in (_lib.EPI_SURRGRAD, _lib.EPI_VFLOSS, _lib.EPI_PPOGRAD):
+            if epi in (_lib.EPI_SURRGRAD, _lib.EPI_VFLOSS, _lib.EPI_PPOGRAD, _lib.EPI_PPOCLIP):
                 mode, cache = _lib.CACHE_WRITE, self._cache(n)
                 self._cache_key = key
             elif epi == _lib.EPI_FVP and self._cache_key == key:
@@ -593,8 +603,9 @@ class LayeredMlpNet:
 
     def rows(self, epi, x, n, ep_t=None, timestep_limit=1.0, inv_n_global=1.0, act=None, adv=None, oldprob=None,
              target=None, out=None, ghead=None, partial=None, theta=None, image=None, tangent=None, image_t=None,
-             skip=None, kl_coeff=0.0, kl_cutoff=0.0, cutoff_coeff=0.0, reverse_kl=0, feat_out=None):
+             skip=None, kl_coeff=0.0, kl_cutoff=0.0, cutoff_coeff=0.0, reverse_kl=0, feat_out=None, clip=None):
         n = int(n)
+        kl_cutoff = _clip_range(epi, clip, kl_cutoff)
         if feat_out is not None and (epi != _lib.EPI_PROB or ep_t is None):
             raise MrlError("feat_out is for the value prediction (EPI_PROB with ep_t)")
         theta = self.theta if theta is None else theta
@@ -611,7 +622,7 @@ class LayeredMlpNet:
             _, X, ldx, H, Z, _ = tape
             dz = self.ws.get("tape_dz", n * self.n_out, torch.float32)
             self._jvp(X, ldx, n, theta, tangent, H, dz, skip)
-        elif epi in (_lib.EPI_SURRGRAD, _lib.EPI_VFLOSS, _lib.EPI_PPOGRAD, _lib.EPI_PPOSGD):
+        elif epi in (_lib.EPI_SURRGRAD, _lib.EPI_VFLOSS, _lib.EPI_PPOGRAD, _lib.EPI_PPOSGD, _lib.EPI_PPOCLIP):
             _, X, ldx, H, Z, _ = self._record(x, n, ep_t, timestep_limit, theta)
         else:
             if n == 0:

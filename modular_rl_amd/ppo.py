@@ -16,6 +16,12 @@ gradient), one VJP and one fused Adam step (``mrl_adam_step``); the epoch
 permutation (host ``np.random.permutation``, as the reference) gathers the rows on
 the device (``mrl_gather_rows``).
 
+``PpoClipUpdater`` is the clipped-surrogate PPO (Schulman et al. 2017, not in the
+reference): ``epochs`` passes of minibatch Adam on ``-mean min(r A, clamp(r, 1 - eps,
+1 + eps) A)``.  The clipped objective has no cross-row term, so its epilogue (PPOCLIP)
+runs on the full row grid at any minibatch size: per minibatch one rows launch, one VJP
+and one fused Adam step, and one host sync per epoch.
+
 Data-parallel: PpoLbfgs all-reduces the loss sums and gradient of every
 evaluation (all ranks take identical L-BFGS steps); PpoSgd averages each
 minibatch gradient over ranks (each rank draws its own minibatches).
@@ -171,20 +177,12 @@ class PpoLbfgsUpdater(_PpoBase):
         return info
 
 
-class PpoSgdUpdater(_PpoBase):
-    options = [
-        ("kl_target", float, 1e-2, ""),
-        ("epochs", int, 10, ""),
-        ("stepsize", float, 1e-3, ""),
-        ("do_split", int, 0, "do train/test split"),
-        ("kl_cutoff_coeff", float, 1000.0, ""),
-    ]
-    BATCHSIZE = _lib.PPO_BLOCK_ROWS
+class _AdamState:
+    """Adam moments and step count on the device, their float32 step size (`ppo.py:240`) and
+    their place in a checkpoint; beside _PpoBase in the minibatch updaters."""
     BETA1, BETA2, EPS = 0.9, 0.999, 1e-8
 
-    def __init__(self, stochpol, usercfg, comm=None):
-        super().__init__(stochpol, usercfg, comm)
-        net = stochpol.net
+    def _adam_init(self, net):
         self.m = torch.zeros(net.P, dtype=torch.float32, device=net.device)
         self.v = torch.zeros(net.P, dtype=torch.float32, device=net.device)
         self.t = 0
@@ -208,6 +206,27 @@ class PpoSgdUpdater(_PpoBase):
         f = np.float32
         t = f(self.t)
         return float(f(self.cfg["stepsize"]) * np.sqrt(f(1) - f(self.BETA2) ** t) / (f(1) - f(self.BETA1) ** t))
+
+    def _adam_step(self, net, g, s):
+        self.t += 1
+        call("mrl_adam_step", ptr(net.theta), ptr(g), ptr(self.m), ptr(self.v), self._a_t(), self.BETA1,
+             self.BETA2, self.EPS, net.P, s)
+        net.pack()
+
+
+class PpoSgdUpdater(_AdamState, _PpoBase):
+    options = [
+        ("kl_target", float, 1e-2, ""),
+        ("epochs", int, 10, ""),
+        ("stepsize", float, 1e-3, ""),
+        ("do_split", int, 0, "do train/test split"),
+        ("kl_cutoff_coeff", float, 1000.0, ""),
+    ]
+    BATCHSIZE = _lib.PPO_BLOCK_ROWS
+
+    def __init__(self, stochpol, usercfg, comm=None):
+        super().__init__(stochpol, usercfg, comm)
+        self._adam_init(stochpol.net)
 
     def update(self, batch):
         cfg, net, comm = self.cfg, self.stochpol.net, self.comm
@@ -255,10 +274,7 @@ class PpoSgdUpdater(_PpoBase):
                 if comm.enabled and comm.world > 1:
                     comm.allreduce_(self.g)
                     self.g.mul_(1.0 / comm.world)
-                self.t += 1
-                call("mrl_adam_step", ptr(net.theta), ptr(self.g), ptr(self.m), ptr(self.v), self._a_t(), self.BETA1,
-                     self.BETA2, self.EPS, net.P, s)
-                net.pack()
+                self._adam_step(net, self.g, s)
             sums = mb_partial.sum(dim=1).cpu().numpy()  # [nmb, 4]
             mb_losses = np.stack([-sums[:, 0] / mb_n, sums[:, 1] / mb_n, sums[:, 2] / mb_n], axis=1)
             train_losses = mb_losses.mean(axis=0)
@@ -270,4 +286,83 @@ class PpoSgdUpdater(_PpoBase):
         info = _info(before, train_losses)
         if cfg["do_split"]:
             info.update(_info(test_before, self._losses(test, n_test), "test_"))
+        return info
+
+
+class PpoClipUpdater(_AdamState, _PpoBase):
+    """PPO with the clipped surrogate: ``epochs`` passes of ``minibatch_size``-row Adam steps
+    on ``-mean min(r A, clamp(r, 1 - clip_param, 1 + clip_param) A)``, r against the
+    rollout-time prob rows (``batch.prob``, as TRPO: no extra forward).  Per minibatch one
+    PPOCLIP rows launch on the full row grid (with the activation cache where the path has
+    one), one VJP and one fused Adam step; the epoch permutation is the host's
+    ``np.random.permutation`` gathered on the device, as PpoSgd; the host reads the epoch's
+    minibatch partial sums once per epoch.  ``target_kl`` > 0 stops after the first epoch
+    whose mean minibatch KL exceeds 1.5 x it.  The info dict's before / after entries are
+    whole-batch LOSSES passes (the plain surrogate -mean r A, KL, entropy) before the update
+    and at the final theta.  The defaults are the conventional PPO ones, not tuned here.  No
+    entropy bonus, no value clipping, no clip-fraction statistic."""
+    options = [
+        ("clip_param", float, 0.2, "clip range of the probability ratio"),
+        ("epochs", int, 10, "passes over the batch"),
+        ("stepsize", float, 3e-4, "Adam step size"),
+        ("minibatch_size", int, 4096, "rows per minibatch: a positive multiple of 128 (the last may be ragged)"),
+        ("target_kl", float, 0.0, "stop after an epoch whose mean minibatch KL exceeds 1.5 x this (0: off)"),
+    ]
+
+    def __init__(self, stochpol, usercfg, comm=None):
+        super().__init__(stochpol, usercfg, comm)
+        bs = int(self.cfg["minibatch_size"])
+        # row buffers are sliced at 128-row multiples: the offsets the row and VJP kernels
+        # (32-row tiles, 16-byte loads) are exercised at
+        if bs <= 0 or bs % _lib.PPO_BLOCK_ROWS != 0:
+            raise _lib.MrlError(f"minibatch_size must be a positive multiple of {_lib.PPO_BLOCK_ROWS} (got {bs})")
+        eps = float(self.cfg["clip_param"])
+        if not 0.0 < eps < 1.0:
+            raise _lib.MrlError(f"clip_param must be in (0, 1) (got {eps})")
+        self._adam_init(stochpol.net)
+
+    def update(self, batch):
+        cfg, net, comm = self.cfg, self.stochpol.net, self.comm
+        if hasattr(batch, "check_abort"):
+            batch.check_abort(comm)  # an aborted persistent rollout never reaches theta
+        N, bs, eps = batch.n, int(cfg["minibatch_size"]), float(cfg["clip_param"])
+        full = _Rows(batch, 0, N)
+        n_glob = comm.allreduce_int(N)
+        before = self._losses(full, n_glob)
+        dev = net.device
+        pobs = torch.empty_like(full.obs)
+        pact = torch.empty_like(full.act)
+        padv = torch.empty_like(full.adv)
+        pold = torch.empty_like(full.prob)
+        ghead = net.ws.get("ppo_ghead", min(bs, N) * net.gh, torch.float32)
+        mb_n = np.array([min(bs, N - i) for i in range(0, N, bs)], dtype=np.float64)
+        prow = net.partial_rows(min(bs, N))  # the largest minibatch's; a ragged one writes fewer rows
+        mb_partial = torch.zeros(len(mb_n), prow, 4, dtype=torch.float64, device=dev)
+        s = stream()
+        epochs_run = 0
+        for _ in range(cfg["epochs"]):
+            perm = torch.as_tensor(np.random.permutation(N).astype(np.int64)).to(dev)
+            for src, dst in ((full.obs, pobs), (full.act, pact), (full.adv, padv), (full.prob, pold)):
+                call("mrl_gather_rows", ptr(src), ptr(perm), N, src[0].numel() * src.element_size(), ptr(dst), s)
+            mb_partial.zero_()
+            for k, i in enumerate(range(0, N, bs)):
+                n = int(mb_n[k])
+                net.rows(_lib.EPI_PPOCLIP, pobs[i:i + n], n, inv_n_global=1.0 / n, act=pact[i:i + n],
+                         adv=padv[i:i + n], oldprob=pold[i:i + n], ghead=ghead, partial=mb_partial[k], clip=eps)
+                net.vjp_flat(pobs[i:i + n], n, ghead, self.g)
+                if comm.enabled and comm.world > 1:
+                    comm.allreduce_(self.g)
+                    self.g.mul_(1.0 / comm.world)
+                self._adam_step(net, self.g, s)
+            epochs_run += 1
+            sums = mb_partial.sum(dim=1).cpu().numpy()  # [minibatches, 4]: the epoch's one host sync
+            mb_kl = float((sums[:, 1] / mb_n).mean())
+            if comm.enabled and comm.world > 1:  # every rank takes the same decision
+                kl_t = torch.as_tensor([mb_kl], dtype=torch.float64, device=dev)
+                comm.allreduce_(kl_t)
+                mb_kl = float(kl_t.cpu().numpy()[0]) / comm.world
+            if cfg["target_kl"] > 0 and mb_kl > 1.5 * cfg["target_kl"]:
+                break
+        info = _info(before, self._losses(full, n_glob))
+        info["epochs_run"] = epochs_run
         return info
